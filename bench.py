@@ -151,6 +151,51 @@ def cpu_baseline_depthnet(algo, S, cfg):
                           cb, S, S, algo, cpu_model(), cores, usable_cores())}
 
 
+DUMP_SAMPLE = 1 << 20              # --dump-outputs: arrays longer than this are written as a seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def collect_outputs(model, out, train):
+    """What the timed path handed its caller in its last step, as float32 host arrays: the returned loss (and loss terms),
+    the logits of both pair directions, and (training) the updated parameters and the gradients of that step from the
+    flat buffers.  Buffers longer than DUMP_SAMPLE elements are sampled at fixed, seeded positions."""
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def put(name, v):
+        if torch.is_tensor(v):
+            v = v.detach().float().cpu().numpy()
+        arrays[name] = np.array(v, dtype=np.float32, order="C")
+
+    logs, res = out if isinstance(out, tuple) else ({}, out)
+    for k, v in list((logs or {}).items()) + list(res.items()):
+        if torch.is_tensor(v) or isinstance(v, (int, float)):
+            put(k, v)
+    if getattr(model, "last_logits", None) is not None:
+        put("logits", model.last_logits)
+    if train:
+        owner = model.net if hasattr(getattr(model, "net", None), "flat_params") else model.optim
+        for name, flat in (("params", owner.flat_params), ("grads", owner.flat_grads)):
+            n = flat.numel()
+            if n > DUMP_SAMPLE:
+                idx = np.sort(np.random.RandomState(0).choice(n, DUMP_SAMPLE, replace=False))
+                put(name + "_sample", flat.reshape(-1)[torch.from_numpy(idx).to(flat.device)])
+            else:
+                put(name, flat)
+    return arrays
+
+
+def dump_outputs(arrays, out_dir):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes over the %d-byte cap" % (total, DUMP_MAX_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "bytes": total, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -185,7 +230,12 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="weak (default, the reference's "
                     "semantics: batch_size is per process, InstaOrderNet_o/config.yaml:49) = --batch pairs per GPU; "
                     "strong = --batch is the GLOBAL pair batch, each of the N ranks takes batch / N of it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed "
+                    "step returned (loss terms, logits; training: the updated parameters and the step's gradients, a "
+                    "seeded sample of %d elements each) as DIR/<name>.npy in float32, rank 0 only" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, the way the reference starts its
     # own workers from one command (main.py:28-35).  The parent has not touched the GPU (no HIP call, no torch
@@ -207,6 +257,7 @@ def main():
     import instaorder_amd as ia
     from instaorder_amd import _lib, engine, synthetic
 
+    torch.manual_seed(0)       # module-default initialisation (InstaDepthNet_*): the same weights on every run
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -350,6 +401,9 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
+    # the last timed step's results, copied out before any later pass (profiling, A/B legs) updates the weights again
+    dumped = dump_outputs(collect_outputs(model, out, args.mode == "train"), args.dump_outputs) \
+        if args.dump_outputs and rank == 0 else None
     ms_median = 0.5 * (step_ms[(len(step_ms) - 1) // 2] + step_ms[len(step_ms) // 2]) if step_ms else None
     hip_graph = bool(getattr(model, "_use_graph", False) and (getattr(model, "_graph", None) is not None
                                                               or getattr(model, "_dp_graphs", None)))
@@ -466,6 +520,8 @@ def main():
         "achieved_tflops_whole_step": pairs_per_s * flop_per_pair / 1e12,
         "mfma_frac_whole_step": pairs_per_s * flop_per_pair / 1e12 / (world * PEAK_FP32_MFMA_TFLOPS),
     }
+    if dumped:
+        result["dump_outputs"] = dumped
     if args.dtype == "bf16":
         # every GEMM of the bf16 step multiplies on v_mfma_f32_32x32x16_bf16 (fp32 accumulate): the whole-step figure against
         # the dense bf16 peak, under its own key -- `mfma_frac_whole_step` stays the fp32-peak figure of the headline line
