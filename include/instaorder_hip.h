@@ -167,6 +167,15 @@ int io_order_loss(const float* logits, int N, int B, int Kocc, int Kdep, const f
 int io_sgd_momentum(float* params, const float* grads, float* momentum_buf, size_t n, float lr, float momentum,
                     float weight_decay, hipStream_t stream);
 
+/* ---- torch.optim.Adam(lr, betas=(beta1, beta2), eps, weight_decay) step over a flat buffer, amsgrad / maximize off
+ * (single_stage_model.py:39-42).  exp_avg / exp_avg_sq: fp32 state of the same layout as params.  One step count for
+ * the whole range: bias_correction1 = 1 - beta1^step, bias_correction2 = 1 - beta2^step, computed by the caller.  lr,
+ * the betas and the bias corrections are doubles because torch forms 1 - beta, lr / bias_correction1 and
+ * sqrt(bias_correction2) in double and rounds each to fp32 once.  n % 4 == 0; 16-byte aligned buffers. */
+int io_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                 double beta2, float eps, float weight_decay, double bias_correction1, double bias_correction2,
+                 hipStream_t stream);
+
 /* ---- whole-network executor: resnet50_cls(in_channels=5, num_classes=K | [K0,K1])
  * (resnet_cls.py:259-268) forward / backward over caller-owned flat buffers. ----------------- */
 typedef struct io_net io_net;

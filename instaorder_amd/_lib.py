@@ -54,6 +54,7 @@ class ProfEntry(C.Structure):
 
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
+_D = C.c_double
 
 # name -> (restype, argtypes); every symbol include/instaorder_hip.h declares
 SIGNATURES = {
@@ -92,6 +93,8 @@ SIGNATURES = {
     "io_pair_planes_u8_hw": (_I, [_P, _Z, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "io_order_loss": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _F, _F, _F, _P, _P, _P]),
     "io_sgd_momentum": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P]),
+    # params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, stream
+    "io_adam_step": (_I, [_P, _P, _P, _P, _Z, _D, _D, _D, _F, _F, _D, _D, _P]),
     "io_net_create": (_P, [_I, _I, C.POINTER(C.c_int)]),
     "io_net_destroy": (None, [_P]),
     "io_net_param_floats": (_L, [_P]),

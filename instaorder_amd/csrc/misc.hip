@@ -1,5 +1,5 @@
 // Small HBM-bound / latency-bound kernels of the order-prediction path: input packing, max-pool,
-// global-average-pool + FC heads, order losses, momentum SGD, filter transposition.
+// global-average-pool + FC heads, order losses, momentum SGD, Adam, filter transposition.
 #include "io_common.h"
 
 #ifndef IO_POOL_ROWS
@@ -499,6 +499,36 @@ __global__ __launch_bounds__(kThreads) void sgd_momentum_kernel(float* __restric
     }
 }
 
+// ---- Adam over the flat parameter buffer (single_stage_model.py:39-42: torch.optim.Adam, amsgrad off) ------------
+// torch's single-tensor Adam, in its order: g += wd*p (coupled L2, wd != 0 only) ; m = lerp(m, g, 1-b1) ;
+// v = b2*v + (1-b2)*g*g ; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps), step_size = lr/bc1.  lerp as torch evaluates
+// it: weight < 0.5 -> m + w*(g-m), else g - (g-m)*(1-w).  28 B of HBM traffic per element.
+__global__ __launch_bounds__(kThreads) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, size_t n4, float w1,
+                                                       float b2, float omb2, float eps, float wd, float step_size,
+                                                       float bc2_sqrt) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const bool small_w = w1 < 0.5f;
+    const float omw1 = 1.f - w1;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 pv = ld4(p + i * 4);
+        f32x4 gv = ld4(g + i * 4);
+        if (wd != 0.f) gv = gv + wd * pv;
+        const f32x4 mv = ld4(m + i * 4);
+        const f32x4 d = gv - mv;
+        const f32x4 mn = small_w ? mv + w1 * d : gv - d * omw1;
+        const f32x4 vn = b2 * ld4(v + i * 4) + omb2 * gv * gv;
+        f32x4 den;
+        den.x = sqrtf(vn.x) / bc2_sqrt + eps;
+        den.y = sqrtf(vn.y) / bc2_sqrt + eps;
+        den.z = sqrtf(vn.z) / bc2_sqrt + eps;
+        den.w = sqrtf(vn.w) / bc2_sqrt + eps;
+        st4(m + i * 4, mn);
+        st4(v + i * 4, vn);
+        st4(p + i * 4, pv - step_size * (mn / den));
+    }
+}
+
 // ---- filter transpose  W[O][T][C] -> Wt[C][T][O]  (operand of the data-gradient GEMM); the source is the
 // fp32 master filter, the destination has the GEMM operand type (bf16 in bf16 mode) --------------------
 template <typename T>
@@ -726,6 +756,23 @@ extern "C" int io_sgd_momentum(float* params, const float* grads, float* momentu
     hipLaunchKernelGGL(sgd_momentum_kernel, dim3(ew_blocks(n4)), dim3(kThreads), 0, st, params, grads, momentum_buf,
                        n4, lr, momentum, weight_decay);
     return io_check_launch("sgd_momentum");
+}
+
+extern "C" int io_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                            double beta1, double beta2, float eps, float weight_decay, double bias_correction1,
+                            double bias_correction2, hipStream_t st) {
+    IO_REQUIRE(n % 4 == 0, IO_ERR_SHAPE, "adam: n=%zu must be a multiple of 4", n);
+    IO_REQUIRE(bias_correction1 > 0.0 && bias_correction2 > 0.0, IO_ERR_SHAPE, "adam: bias corrections %g %g must be > 0",
+               bias_correction1, bias_correction2);
+    const size_t n4 = n / 4;
+    // as torch: 1 - beta, lr / bc1 and sqrt(bc2) in double, each rounded to fp32 once
+    const float step_size = (float)(lr / bias_correction1);
+    const float bc2_sqrt = (float)sqrt(bias_correction2);
+    IoProfScope prof(IO_PROF_ADAM, 0.0, 28.0 * n, st);
+    if (n4 == 0) return IO_OK;
+    hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n4)), dim3(kThreads), 0, st, params, grads, exp_avg, exp_avg_sq, n4,
+                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, weight_decay, step_size, bc2_sqrt);
+    return io_check_launch("adam");
 }
 
 int io_filter_prepare_t(const float* w, int O, int T, int C, void* dst, int transpose, hipStream_t st, int dt) {

@@ -180,6 +180,25 @@ def sgd_momentum(params, grads, buf, lr, momentum, weight_decay):
                                           float(momentum), float(weight_decay), _stream()), "io_sgd_momentum")
 
 
+def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, begin=0, end=None):
+    """torch.optim.Adam's update of the elements [begin, end) of the flat fp32 buffers, all at step count ``step``
+    (>= 1, the count after this update); the bias corrections are computed here in double, as torch does."""
+    _lib.require_gpu()
+    end = params.numel() if end is None else end
+    for t in (grads, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == params.numel()
+    assert params.dtype == torch.float32 and params.is_contiguous() and 0 <= begin <= end <= params.numel()
+    assert begin % 4 == 0, "adam_step: begin must keep 16-byte alignment"
+    bc1 = 1.0 - float(beta1) ** int(step)
+    bc2 = 1.0 - float(beta2) ** int(step)
+
+    def at(t):
+        return C.c_void_p(t.data_ptr() + 4 * begin)
+    _lib.check(_lib.lib().io_adam_step(at(params), at(grads), at(exp_avg), at(exp_avg_sq), end - begin, float(lr),
+                                       float(beta1), float(beta2), float(eps), float(weight_decay), bc1, bc2, _stream()),
+                                       "io_adam_step")
+
+
 _prof_on = False
 
 

@@ -40,7 +40,7 @@ class WeightPlan(object):
 
     Built from a RECORDING of one eager training step (which filters are used, with which stored channel counts), so
     it needs no knowledge of the module tree; a filter used more than once per step stays on the per-call path (its
-    gradients must accumulate).  Only for parameters that live in a flat buffer (optim.FlatSGD)."""
+    gradients must accumulate).  Only for parameters that live in a flat buffer (optim.FlatSGD, optim.FlatAdam)."""
     active = None          # the plan convolutions consult (set for the duration of a training step)
     _recording = None      # id(w) -> [w, Cip, Cop, uses] while a step is being recorded
 

@@ -7,6 +7,10 @@ a ``torch.optim.Optimizer`` (utils/scheduler.py:7-9 type-checks it and rewrites
 ``param_groups[i]['lr']``), and its ``state_dict`` has torch.optim.SGD's layout (one
 ``momentum_buffer`` per parameter) so checkpoints interchange with the reference
 (single_stage_model.py:66-72).  The update itself is one HIP launch over 23.5 M floats.
+
+FusedAdam / FlatAdam do the same for ``optim: Adam`` (single_stage_model.py:39-42, torch.optim.Adam with
+betas=(beta1, 0.999)) over the same two flat layouts: torch.optim.Adam's state_dict layout, per-parameter step counts,
+parameters without a gradient skipped as torch skips them.
 """
 import torch
 
@@ -78,27 +82,28 @@ class FusedSGD(torch.optim.Optimizer):
                         self._views[int(i)].copy_(mb)
 
 
-class FlatSGD(torch.optim.Optimizer):
-    """Momentum-SGD for an ordinary module tree (the MiDaS branch): the parameters are moved into ONE flat fp32
-    buffer (each ``nn.Parameter`` becomes a view of it), so the update is the same single HIP launch as FusedSGD;
-    the gradients autograd produced per tensor are gathered into a flat buffer first (that buffer is also what the
-    data-parallel all-reduce runs on).  torch.optim.SGD semantics / state_dict layout as above."""
+def _trainable(module):
+    params = []
+    seen = set()
+    for p in module.parameters():
+        if id(p) not in seen and p.requires_grad:
+            seen.add(id(p))
+            params.append(p)
+    return params
 
-    def __init__(self, module, lr, momentum=0.9, weight_decay=0.0):
-        params = []
-        seen = set()
-        for p in module.parameters():
-            if id(p) not in seen and p.requires_grad:
-                seen.add(id(p))
-                params.append(p)
-        defaults = dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False)
-        super(FlatSGD, self).__init__(params, defaults)
+
+class _FlatLayout(torch.optim.Optimizer):
+    """An ordinary module tree (the MiDaS branch) moved into ONE flat fp32 buffer: each ``nn.Parameter`` becomes a view
+    of it (spans padded to 64 floats), so an optimiser update is one HIP launch; the gradients autograd produced per
+    tensor are gathered into a flat buffer first (that buffer is also what the data-parallel all-reduce runs on)."""
+
+    def __init__(self, params, defaults):
+        super(_FlatLayout, self).__init__(params, defaults)
         self._params = params
         n = sum(((p.numel() + 63) // 64) * 64 for p in params)
         dev = params[0].device
         self.flat_params = torch.zeros(n, device=dev)
         self.flat_grads = torch.zeros(n, device=dev)
-        self._buf = torch.zeros(n, device=dev)
         self._spans = []
         off = 0
         with torch.no_grad():
@@ -155,6 +160,16 @@ class FlatSGD(torch.optim.Optimizer):
                 return off
         raise KeyError("parameter is not in the flat buffer")
 
+
+class FlatSGD(_FlatLayout):
+    """Momentum-SGD over the flat layout of _FlatLayout: the update is the same single HIP launch as FusedSGD.
+    torch.optim.SGD semantics / state_dict layout as above."""
+
+    def __init__(self, module, lr, momentum=0.9, weight_decay=0.0):
+        defaults = dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False)
+        super(FlatSGD, self).__init__(_trainable(module), defaults)
+        self._buf = torch.zeros_like(self.flat_params)
+
     @torch.no_grad()
     def step(self, closure=None, gathered=False):
         g = self.param_groups[0]
@@ -182,3 +197,220 @@ class FlatSGD(torch.optim.Optimizer):
                 if mb is not None:
                     off, k = self._spans[int(i)]
                     self._buf[off:off + k].copy_(mb.reshape(-1))
+
+
+# ---- Adam ----------------------------------------------------------------------------------------------------------
+# param-group keys torch.optim.Adam may carry that change nothing here, and those that must keep torch's default
+_ADAM_INERT = ("foreach", "fused", "capturable", "differentiable", "initial_lr")
+_ADAM_OFF = ("amsgrad", "maximize", "decoupled_weight_decay")
+
+
+def _adam_defaults(lr, betas, eps, weight_decay):
+    """The installed torch's Adam param group (same key set as its state_dict writes), with these hyper-parameters;
+    torch's own constructor validates them."""
+    probe = torch.optim.Adam([torch.zeros(1, requires_grad=True)], lr=lr, betas=betas, eps=eps,
+                             weight_decay=weight_decay)
+    return {k: v for k, v in probe.param_groups[0].items() if k != "params"}
+
+
+class _AdamFlat(object):
+    """torch.optim.Adam (amsgrad / maximize off, coupled L2) over a flat fp32 parameter buffer; mixed into a
+    torch.optim.Optimizer.  The subclass provides ``_params`` (group order), ``_begin[i]`` (float offset of parameter i's
+    storage, 16-byte aligned, increasing with i), ``_flat()`` -> (params, grads) and ``_state_view(buf, i)``.
+
+    State per parameter as torch keeps it: ``step`` (an int here), ``exp_avg`` / ``exp_avg_sq`` (slices of two flat
+    buffers).  A parameter without a gradient in a step (``_live[i]`` False) is skipped: value, moments and step count
+    stay, and it has no state entry before its first gradient.  The launches cover runs of consecutive parameters that
+    take the update with one step count; a parameter that never had a gradient joins any run when weight_decay is 0 --
+    its gradient slice, exp_avg and exp_avg_sq are all zero, so the update leaves all three bit-identical
+    (m = lerp(0, 0) = 0, v = 0, p -= step_size * 0 / eps).  Hence the usual step is ONE launch over the whole buffer."""
+
+    def _adam_layout(self):
+        n = len(self._params)
+        self._steps = [0] * n
+        self._live = [True] * n
+        self._exp_avg = None
+        self._exp_avg_sq = None
+        if any(b % 4 for b in self._begin) or any(a >= b for a, b in zip(self._begin, self._begin[1:])):
+            raise ValueError("flat Adam: parameter storage must be 16-byte aligned and in buffer order")
+
+    def _ensure_state(self):
+        flat, _ = self._flat()
+        if self._exp_avg is None or self._exp_avg.device != flat.device:
+            old = (self._exp_avg, self._exp_avg_sq)
+            self._exp_avg, self._exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
+            if old[0] is not None:
+                self._exp_avg.copy_(old[0])
+                self._exp_avg_sq.copy_(old[1])
+        return self._exp_avg, self._exp_avg_sq
+
+    @staticmethod
+    def _check_group(group):
+        bad = [k for k in _ADAM_OFF if group.get(k)]
+        if bad:
+            raise ValueError("flat Adam supports torch.optim.Adam with %s off (got %s)"
+                             % (" / ".join(_ADAM_OFF), ", ".join("%s=%r" % (k, group[k]) for k in bad)))
+        unknown = set(group) - set(("params", "lr", "betas", "eps", "weight_decay") + _ADAM_OFF + _ADAM_INERT)
+        if unknown:
+            raise ValueError("flat Adam: param-group keys it cannot honour: %s" % sorted(unknown))
+
+    def _runs(self, weight_decay):
+        """[(first, last, step)] over the parameters in group order: parameters first..last take this update with step
+        count ``step`` (after it)."""
+        n = len(self._params)
+        live, steps = self._live, self._steps
+        if all(live) and steps.count(steps[0]) == n:
+            return [(0, n - 1, steps[0] + 1)]
+        runs = []
+        cur, pend = None, None          # cur = [first, last, step]; pend: first of a streak of never-stepped, gradient-less
+        for i in range(n):
+            if live[i]:
+                t = steps[i] + 1
+                if cur is not None and cur[2] == t:
+                    cur[1] = i
+                else:
+                    if cur is not None:
+                        runs.append(tuple(cur))
+                    cur = [i if pend is None else pend, i, t]
+                pend = None
+            elif steps[i] == 0 and weight_decay == 0:
+                if pend is None:
+                    pend = i
+            else:
+                if cur is not None:
+                    runs.append(tuple(cur))
+                cur, pend = None, None
+        if cur is not None:
+            runs.append(tuple(cur))
+        return runs
+
+    def _adam_update(self):
+        g = self.param_groups[0]
+        self._check_group(g)
+        flat_p, flat_g = self._flat()
+        m, v = self._ensure_state()
+        b1, b2 = g["betas"]
+        n = len(self._params)
+        for first, last, t in self._runs(g["weight_decay"]):
+            end = self._begin[last + 1] if last + 1 < n else flat_p.numel()
+            engine.adam_step(flat_p, flat_g, m, v, g["lr"], b1, b2, g["eps"], g["weight_decay"], t,
+                             self._begin[first], end)
+        self._steps = [s + 1 if l else s for s, l in zip(self._steps, self._live)]
+
+    # ---- checkpoint interchange with torch.optim.Adam --------------------------------------------------------------
+    def state_dict(self):
+        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(len(self._params)))
+        state = {}
+        for i, s in enumerate(self._steps):
+            if s > 0:
+                state[i] = {"step": torch.tensor(float(s)),
+                            "exp_avg": self._state_view(self._exp_avg, i).detach().clone().contiguous(),
+                            "exp_avg_sq": self._state_view(self._exp_avg_sq, i).detach().clone().contiguous()}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        """A state_dict of torch.optim.Adam (any torch since 1.7: ``step`` an int or a 0-d tensor) or of this class."""
+        if len(sd["param_groups"]) != 1:
+            raise ValueError("flat Adam has one parameter group, the checkpoint has %d" % len(sd["param_groups"]))
+        grp = sd["param_groups"][0]
+        self._check_group(grp)
+        ids = list(grp["params"])
+        if len(ids) != len(self._params):
+            raise ValueError("checkpoint optimiser holds %d parameters, this model %d" % (len(ids), len(self._params)))
+        where = {pid: i for i, pid in enumerate(ids)}
+        m, v = self._ensure_state()
+        steps = [0] * len(self._params)
+        with torch.no_grad():
+            m.zero_()
+            v.zero_()
+            for pid, st in sd["state"].items():
+                i = where[pid]
+                s = st["step"]
+                steps[i] = int(s.item()) if torch.is_tensor(s) else int(s)
+                self._state_view(m, i).copy_(st["exp_avg"])
+                self._state_view(v, i).copy_(st["exp_avg_sq"])
+        self._steps = steps
+        for k, val in grp.items():
+            if k != "params":
+                self.param_groups[0][k] = tuple(val) if k == "betas" else val
+
+
+class FusedAdam(_AdamFlat, torch.optim.Optimizer):
+    """torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay) for the instaorder_amd ResNet: the update runs
+    over its flat fp32 master buffers (``flat_params`` / ``flat_grads``, in fp32 and bf16 mode alike)."""
+
+    def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        net = getattr(module, "module", module)     # DistModule / FixModule wrap the ResNet
+        if not hasattr(net, "flat_params"):
+            raise TypeError("FusedAdam needs an instaorder_amd ResNet (flat parameter buffer)")
+        self._net = net
+        params = list(net.parameters())
+        super(FusedAdam, self).__init__(params, _adam_defaults(lr, betas, eps, weight_decay))
+        if len(self.param_groups) != 1:
+            raise ValueError("FusedAdam supports exactly one parameter group")
+        info = {id(p): t for t, p in net._param_list}
+        self._params = params
+        self._info = [info[id(p)] for p in params]
+        self._begin = [t["offset"] for t in self._info]
+        self._adam_layout()
+
+    def _flat(self):
+        return self._net.flat_params, self._net.flat_grads
+
+    def _state_view(self, buf, i):
+        return self._net._view(buf, self._info[i])
+
+    def zero_grad(self, set_to_none=True):
+        # gradients are rewritten in full by every backward of the engine; nothing to clear
+        for p in self.param_groups[0]["params"]:
+            if set_to_none:
+                p.grad = None
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise ValueError("FusedAdam: closures are not supported")
+        self._live = [p.grad is not None for p in self._params]
+        self._adam_update()
+        return None
+
+
+class FlatAdam(_AdamFlat, _FlatLayout):
+    """torch.optim.Adam for an ordinary module tree (the MiDaS nets) over the flat layout FlatSGD uses, so ops.WeightPlan,
+    the hipGraph step and the staged data-parallel step take it as they take FlatSGD.  Which parameters had a gradient
+    is what the last gather_grads / gather_stage saw (a parameter ops.WeightPlan fills counts as having one); a replayed
+    hipGraph keeps what its capture saw."""
+
+    def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        super(FlatAdam, self).__init__(_trainable(module), _adam_defaults(lr, betas, eps, weight_decay))
+        self._begin = [off for off, _ in self._spans]
+        self._adam_layout()
+        self._ensure_state()
+
+    def _flat(self):
+        return self.flat_params, self.flat_grads
+
+    def _state_view(self, buf, i):
+        off, k = self._spans[i]
+        return buf[off:off + k].view(self._params[i].shape)
+
+    def gather_grads(self, skip=None, prezeroed=False):
+        self._live = [p.grad is not None or (skip is not None and id(p) in skip) for p in self._params]
+        return super(FlatAdam, self).gather_grads(skip=skip, prezeroed=prezeroed)
+
+    def gather_stage(self, idx, grads, skip=None, attach=False, prezeroed=False):
+        for i, g in zip(idx, grads):
+            self._live[i] = g is not None or (skip is not None and id(self._params[i]) in skip)
+        return super(FlatAdam, self).gather_stage(idx, grads, skip=skip, attach=attach, prezeroed=prezeroed)
+
+    @torch.no_grad()
+    def step(self, closure=None, gathered=False):
+        if closure is not None:
+            raise ValueError("FlatAdam: closures are not supported")
+        if not gathered:
+            self.gather_grads()
+        self._adam_update()
+        from . import ops
+        ops.WEIGHTS_EPOCH[0] += 1          # parameters changed in place, invisibly to torch's version counters
+        return None

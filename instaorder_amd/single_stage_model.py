@@ -11,7 +11,7 @@ import torch
 import torch.distributed as dist
 
 from . import common_utils, distributed_utils, midas_net, resnet_cls
-from .optim import FlatSGD, FusedSGD
+from .optim import FlatAdam, FlatSGD, FusedAdam, FusedSGD
 
 _BACKBONES = {"resnet50_cls": resnet_cls.resnet50_cls}
 
@@ -46,9 +46,10 @@ class SingleStageModel(object):
             self.optim = FusedSGD(self.model, lr=params["lr"], momentum=0.9,
                                   weight_decay=params["weight_decay"])
         elif params["optim"] == "Adam":
-            # not on the measured path: plain torch Adam over the strided parameter views
-            self.optim = torch.optim.Adam(self.model.parameters(), lr=params["lr"],
-                                          betas=(params["beta1"], 0.999))
+            # single_stage_model.py:39-41: torch.optim.Adam(lr, betas=(beta1, 0.999)); params['weight_decay'] is not
+            # passed there either, so Adam runs without weight decay
+            cls = FusedAdam if hasattr(net, "flat_params") else FlatAdam
+            self.optim = cls(self.model, lr=params["lr"], betas=(params["beta1"], 0.999))
         else:
             raise Exception("No such optimizer: {}".format(params["optim"]))
 

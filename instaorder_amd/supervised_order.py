@@ -506,7 +506,7 @@ class _DepthBase(SingleStageModel):
     def _fwd_loss_bwd(self):
         """forward (both mask orders) + the five loss terms + backward + gradients gathered into the flat buffer"""
         from . import ops
-        flat = hasattr(self.optim, "gather_grads")          # FlatSGD; torch.optim.Adam keeps per-tensor gradients
+        flat = hasattr(self.optim, "gather_grads")          # FlatSGD / FlatAdam; a torch optimiser keeps per-tensor gradients
         plan = self._wplan if (self._wplan and self.PAIR_MODE and self._wplan.dtype == self.net._act_dtype()) else None
         recording = self._wplan is None and self.PAIR_MODE and hasattr(self.optim, "_spans")
         if recording:
@@ -541,7 +541,7 @@ class _DepthBase(SingleStageModel):
     STAGE_NAMES = ("heads+order branches+decoder", "encoder layer4", "encoder layer3", "encoder layer2+layer1")
 
     def grad_stage_slices(self):
-        """[lo, hi) of the flat gradient buffer (optim.FlatSGD) that each backward stage finalises, in execution order.
+        """[lo, hi) of the flat gradient buffer (optim.FlatSGD / FlatAdam) that each backward stage finalises, in execution order.
         The parameters lie in creation order -- encoder layer1..layer4, decoder (scratch), order branches, heads -- and
         the backward pass walks them back to front, so a stage is one contiguous slice: everything behind the encoder
         (the order branches hang off l1..l3, the decoder off l1..l4), then encoder layer4, layer3, layer2 + layer1."""
@@ -641,7 +641,7 @@ class _DepthBase(SingleStageModel):
         yield 3
 
     def _step_overlapped(self):
-        """world_size > 1 (FlatSGD): the step of supervised_order.py:198-209 with the gradient exchange
+        """world_size > 1 (FlatSGD / FlatAdam): the step of supervised_order.py:198-209 with the gradient exchange
         (utils/distributed_utils.py:27-31) cut into the four stage buckets of grad_stage_slices() and overlapped with the
         rest of the backward pass -- the 610 MB of InstaDepthNet_od's gradients are on the wire while the encoder's
         backward (most of the pass) still runs.  Second step of a shape: one hipGraph PER STAGE, replayed afterwards with
@@ -724,7 +724,8 @@ class _DepthBase(SingleStageModel):
         if not self.model.training:
             raise RuntimeError("step() needs switch_to('train')")
         if not hasattr(self.optim, "gather_grads"):
-            # `optim: Adam` (single_stage_model.py:39-41): plain torch optimiser over the per-tensor gradients
+            # a plain torch optimiser over the per-tensor gradients (SingleStageModel builds FlatSGD / FlatAdam, which take
+            # the flat paths below; this serves any other optimiser object put in .optim)
             logs, loss = self._fwd_loss_bwd()
             if self.world_size > 1:
                 distributed_utils.average_gradients(self.model)
