@@ -8,9 +8,13 @@ all-reduce (N>1), SGD.  Inputs are resident in HBM before the timed region.  N>1
 (torch.distributed.run), pairs sharded by rank = B pairs per GPU (weak scaling), one flat RCCL
 all-reduce of the 94 MB gradient per step.
 
-Prints ONE JSON line (rank 0).  ``roofline`` is for the dominant kernel class (by GPU time), timed with
-HIP events on the launch stream inside the timed region; ``cpu_baseline`` times the CPU oracle
-(plain-PyTorch restatement of the reference, pinned by tests/golden) on the host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, writes --dump-outputs and
+prints the line: nothing else.  ``--full`` adds, after the timed region, everything that is not the
+headline figure: the profiled eager pass (``kernel_classes``, ``roofline`` for the dominant kernel class
+by GPU time, timed with HIP events on the launch stream), ``fwd_only``, the ``secondary`` workloads, the
+N>1 exchange A/B (``distributed.overlap_ab``) and ``cpu_baseline`` (the CPU oracle, a plain-PyTorch
+restatement of the reference pinned by tests/golden, on the host cores); each ``--no-*`` flag leaves
+its part out of a ``--full`` run.
 """
 import argparse
 import json
@@ -58,7 +62,7 @@ def cpu_model():
 CPU_BASELINE_MAX_THREADS = 32
 
 
-CPU_BASELINE_BUDGET_S = 20.0       # bounded sample: about 10-30 s of CPU work per default bench run (the whole default run stays near 40 s)
+CPU_BASELINE_BUDGET_S = 20.0       # bounded sample: about 10-30 s of CPU work per --full run
 
 
 def cpu_baseline(sd, S):
@@ -219,12 +223,16 @@ def main():
                     "batch (default); images20 = BASELINE configs[3]: synthetic 20-instance images, all 190 pairs of "
                     "every image enumerated (upper triangle, image-major), the pair list sharded contiguously across "
                     "ranks, each step gathers its pair batch from the instance masks on the device")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="skip the per-kernel HIP-event timing")
-    ap.add_argument("--no-overlap-ab", action="store_true", help="N > 1: skip the extra pass with the flat gradient exchange")
-    ap.add_argument("--no-fwd-only", action="store_true", help="skip the forward-only secondary measurement of the default line")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads (bf16 at 256 pairs, fp32 at 32 "
-                    "pairs) the default line measures after its timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what is not the headline "
+                    "figure: the profiled per-kernel pass (kernel_classes, roofline), fwd_only, the secondary workloads, the "
+                    "N > 1 exchange A/B and the CPU baseline.  Off by default: a plain run only times its steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-prof", action="store_true", help="--full: skip the per-kernel HIP-event timing")
+    ap.add_argument("--no-overlap-ab", action="store_true", help="--full, N > 1: skip the extra pass with the flat gradient "
+                    "exchange")
+    ap.add_argument("--no-fwd-only", action="store_true", help="--full: skip the forward-only secondary measurement")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary workloads (bf16 at 256 pairs, "
+                    "fp32 at 32 pairs) measured after the timed region of the headline configuration")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to "
                     "exercise the multi-rank path when several ranks must share one GPU)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="weak (default, the reference's "
@@ -411,7 +419,7 @@ def main():
     # groups to bracket) with one HIP event per launch group on the launch stream.  Its step time is stated next to the
     # timed region's so that "class time <= step time" can be checked against either.
     prof, prof_steps, prof_dt = {}, 0, 0.0
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         prof_steps = max(1, min(args.steps, 6))
         one_step()                                   # (an eager step after replays: re-warm the allocator pool)
         torch.cuda.synchronize()
@@ -443,7 +451,7 @@ def main():
     # A/B of the exchange form (N > 1, training): the same steps with ONE flat all-reduce after the whole backward
     # (IO_COMM_OVERLAP=0's path) instead of the stage buckets launched under it -- after the timed region, never part of `value`
     overlap_ab = None
-    if world > 1 and args.mode == "train" and getattr(model, "_overlap_comm", False) and not args.no_overlap_ab:
+    if args.full and world > 1 and args.mode == "train" and getattr(model, "_overlap_comm", False) and not args.no_overlap_ab:
         arena = 0 if depthnet else model.net.plan.workspace_bytes(2 * B, S, True)
         if arena < 100 * 2 ** 30:            # the flat path captures its own graph on a second arena: it must fit beside the first
             model._overlap_comm = False
@@ -501,8 +509,10 @@ def main():
                    **({"precision_note": "bf16 is not a reference precision: parity bar <= 2e-2 on logits (tests/test_gpu_bf16.py); "
                                          "the 0.1 pp accuracy bar of BASELINE.json is claimed for fp32 only"}
                       if args.dtype == "bf16" else {}),
-                   "timed_region": "unprofiled product path (%s); kernel_classes / roofline come from a separate profiled pass "
-                                   "of eager steps, see `profiled`" % ("hipGraph replay" if hip_graph else "eager launches"),
+                   "timed_region": "unprofiled product path (%s)%s" % (
+                       "hipGraph replay" if hip_graph else "eager launches",
+                       "; kernel_classes / roofline come from a separate profiled pass of eager steps, see `profiled`"
+                       if prof else ""),
                    "collective": None if world == 1 else (
                        "%s all-reduce (SUM) of the %d gradient floats in %d stage buckets (%s MB: heads+layer4, layer3, "
                        "layer2, layer1+stem), each launched when its stage of the backward pass is enqueued" % (
@@ -540,7 +550,7 @@ def main():
     # the north-star forward target (BASELINE.json: >= 40 % MFMA on the ResNet-50 pairwise forward at batch 256) as a
     # driver-observed value: the two directional passes + loss in training mode (batch statistics), same inputs, measured
     # AFTER the timed region (rank 0's GPU; every rank runs it so that nobody waits at a collective)
-    if args.mode == "train" and not depthnet and not args.no_fwd_only and not args.host_inputs and pair_src is None:
+    if args.full and args.mode == "train" and not depthnet and not args.no_fwd_only and not args.host_inputs and pair_src is None:
         def fwd_step():
             if args.algo == "InstaOrderNet_o":
                 model.set_input(dev["rgb"], dev["modal1"], dev["modal2"], dev["occ_order"])
@@ -571,7 +581,7 @@ def main():
     # (experiments/InstaOrder/InstaOrderNet_o/config.yaml:49) in fp32 -- replayed steps of the product path, as the headline.
     headline = (args.algo == "InstaOrderNet_o" and B == 256 and S == 256 and args.mode == "train" and args.dtype == "fp32"
                 and world == 1 and not args.host_inputs and pair_src is None)
-    if headline and not args.no_secondary:
+    if args.full and headline and not args.no_secondary:
         def secondary_leg(dtype, b2, nsteps=5):
             cfg2 = dict(cfg, dtype=dtype)
             m2 = ia.InstaOrderNet_o(cfg2, dist_model=False)
@@ -713,7 +723,7 @@ def main():
             if result.get("mfma_frac_whole_step") is not None:
                 result["mfma_frac_whole_step_executed"] = result["mfma_frac_whole_step"] * fl_exe / fl_alg
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "train":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "train":
         result["cpu_baseline"] = cpu_baseline_depthnet(args.algo, S, cfg) if depthnet else cpu_baseline(sd, S)
     if rank == 0:
         print(json.dumps(result))

@@ -7,7 +7,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 for r in $(seq 1 "$ROUNDS"); do
   for v in "$@"; do
     if [ "$v" = default ]; then unset IO_LIB_PATH; else export IO_LIB_PATH="$ROOT/instaorder_amd/libinstaorder_hip_$v.so"; fi
-    python "$ROOT/bench.py" $ARGS --no-cpu-baseline 2>/dev/null | python -c "
+    python "$ROOT/bench.py" $ARGS --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 kc=d.get('kernel_classes',{})
