@@ -339,6 +339,25 @@ size_t io_disp_order_workspace_floats(int B, int H, int W);
 int io_disp_order_count(const float* disp1, const float* disp2, const float* modal1, const float* modal2,
                         const long* depth_order1, const long* is_overlap, int B, int H, int W, int le_order,
                         float out_scale, float* out, float* workspace, size_t workspace_floats, hipStream_t stream);
+/* ---- dense-disparity evaluation (tools/test_disp_KITTI.py, tools/test_disp_DIW.py) -------------------------------------
+ * io_depth_errors_median: the "median" branch of test_disp_KITTI.py:eval_dense_depth + Tester.compute_errors for B images
+ * at once.  pred[B][H][W] fp32 disparity, gt[B][H][W] raw uint16 ground truth; per image, in fp32 as the reference:
+ * g = float(gt) / gt_div, valid = min_depth <= g <= max_depth, depth = 1 / ((pred - min pred) / max pred + 1e-3) over the
+ * whole map, ratio = median(g[valid]) / median(depth[valid]) (NumPy's median, exact), depth = clamp(depth * ratio,
+ * min_depth, max_depth); the errors are means over valid with fp64 sums.  out[B][10] (fp64): abs_rel, sq_rel, rmse,
+ * rmse_log, a1, a2, a3, silog, n_valid, ratio; an image without a valid pixel gives NaN (n_valid 0).  medians (optional,
+ * [B][2] fp32): the two medians.  A row depends on its image only (bitwise, for any B).  Six launches; workspace:
+ * io_depth_errors_median_workspace_bytes(B, H, W) bytes. */
+size_t io_depth_errors_median_workspace_bytes(int B, int H, int W);
+int io_depth_errors_median(const float* pred, const uint16_t* gt, int B, int H, int W, float gt_div, float min_depth,
+                           float max_depth, double* out, float* medians, void* workspace, size_t workspace_bytes,
+                           hipStream_t stream);
+/* io_disp_sample_points: for each image b of disp[B][H][W] (fp32) and points[b] = {h, w, Ay, Ax, By, Bx} (int32), the values
+ * of F.interpolate(disp[b], size=(h, w), mode='bilinear', align_corners=False) at A and B -- values[b] = {dA, dB}, without
+ * forming the upsampled map -- and decisions[b] = '<' if dA > dB, '>' if dA < dB, '=' if equal (test_disp_DIW.py:130-142),
+ * 0 otherwise (NaN).  Points are clamped into the h x w map. */
+int io_disp_sample_points(const float* disp, int B, int H, int W, const int* points, float* values, int* decisions,
+                          hipStream_t stream);
 /* io_conv2d_fwd_bnstats for either storage type and for the grouped window form (gw = 64; w = wc of io_gconv_pack,
  * Cin == Cout); gw = 0 is the dense convolution */
 int io_conv2d_fwd_bnstats_dt(const void* x, const void* w, void* y, int N, int H, int W, int Cin, int Cout, int R, int S,

@@ -176,6 +176,10 @@ SIGNATURES = {
     "io_maxpool_bwd_dt": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "io_avgpool_fc_fwd_dt": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P]),
     "io_avgpool_fc_bwd_dt": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    # pred, gt (uint16), B, H, W, gt_div, min_depth, max_depth, out (fp64 [B][10]), medians, workspace, workspace_bytes, stream
+    "io_depth_errors_median_workspace_bytes": (_Z, [_I, _I, _I]),
+    "io_depth_errors_median": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _Z, _P]),
+    "io_disp_sample_points": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "io_prof_begin": (_I, []),
     "io_prof_begin_ex": (_I, [_I]),
     "io_prof_end": (_I, [C.POINTER(ProfEntry), _I]),

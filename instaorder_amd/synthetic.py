@@ -336,3 +336,76 @@ def make_depth_batch(seed, B, S):
     b["is_overlap"] = (np.arange(B) % 2).astype(np.int64)
     b["depth_order"] = (np.arange(B) % 3).astype(np.int64)
     return b
+
+
+# ---- mini KITTI / DIW sets for the dense-disparity evaluation (instaorder_amd.dense_eval) --------------------------------
+MINI_KITTI_SIZES = ((375, 1242), (370, 1224), (376, 1241))     # real KITTI raw sizes; image 1 has no ground truth
+MINI_DIW_SIZES = ((240, 320), (320, 240), (180, 180), (500, 375), (97, 151), (384, 384))
+
+
+def dense_disparities(seed, n, H, W):
+    """n fixed disparity maps [n,H,W] fp32: uint16 / 1000 (so many values tie)."""
+    rs = np.random.RandomState(seed)
+    return (rs.randint(0, 65536, size=(n, H, W)).astype(np.uint16) / np.float32(1000)).astype(np.float32)
+
+
+def sparse_gt_u16(rs, H, W, density=0.05, max_raw=90 * 256):
+    """KITTI-like raw uint16 ground truth: ~`density` of the pixels set to 1..max_raw (some beyond 80 m), the rest 0."""
+    g = np.zeros((H, W), np.uint16)
+    on = rs.rand(H, W) < density
+    g[on] = rs.randint(1, max_raw + 1, size=int(on.sum())).astype(np.uint16)
+    return g
+
+
+def write_mini_kitti(root, seed):
+    """<root>/rawdata/... images, <root>/data_depth_annotated/... 16-bit PNGs and <root>/eigen_test.txt (one entry names
+    a ground truth that does not exist, as the Eigen list does with `None`).  Returns the list file's path."""
+    import os
+    from PIL import Image
+    rs = np.random.RandomState(seed)
+    lines = []
+    for k, (H, W) in enumerate(MINI_KITTI_SIZES):
+        drive = "2011_09_26/2011_09_26_drive_%04d_sync" % (k + 1)
+        img_rel = "%s/image_02/data/%010d.png" % (drive, 5 * k)
+        gt_rel = "%s/proj_depth/groundtruth/image_02/%010d.png" % (drive.split("/")[1], 5 * k) if k != 1 else "None"
+        img = rs.randint(0, 256, size=(H, W, 3)).astype(np.uint8)
+        p = os.path.join(root, "rawdata", img_rel)
+        os.makedirs(os.path.dirname(p), exist_ok=True)
+        Image.fromarray(img).save(p)
+        gt = sparse_gt_u16(rs, H, W)
+        if gt_rel != "None":
+            p = os.path.join(root, "data_depth_annotated", gt_rel)
+            os.makedirs(os.path.dirname(p), exist_ok=True)
+            Image.fromarray(gt).save(p)
+        lines.append("%s %s 721.5377" % (img_rel, gt_rel))
+    lst = os.path.join(root, "eigen_test.txt")
+    with open(lst, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return lst
+
+
+def write_mini_diw(root, seed):
+    """<root>/DIW_test/*.thumb (PNG data; one grayscale) and <root>/DIW_test.csv: an image line, then a point line
+    `A_y,A_x,B_y,B_x,ordinal,...` with 1-based points.  The last sample has A == B and the ordinal '='.  Returns the csv."""
+    import os
+    from PIL import Image
+    rs = np.random.RandomState(seed)
+    os.makedirs(os.path.join(root, "DIW_test"), exist_ok=True)
+    lines = []
+    for k, (h, w) in enumerate(MINI_DIW_SIZES):
+        fn = "./DIW_test/%08x.thumb" % (0x1000 + 17 * k)
+        img = rs.randint(0, 256, size=(h, w, 3)).astype(np.uint8)
+        im = Image.fromarray(img)
+        if k == 2:
+            im = im.convert("L")
+        im.save(os.path.join(root, fn[2:]), format="PNG")
+        ay, ax, by, bx = rs.randint(1, h + 1), rs.randint(1, w + 1), rs.randint(1, h + 1), rs.randint(1, w + 1)
+        o = "<>"[rs.randint(0, 2)]
+        if k == len(MINI_DIW_SIZES) - 1:
+            by, bx, o = ay, ax, "="
+        lines.append(fn)
+        lines.append("%d,%d,%d,%d,%s,%d,%d" % (ay, ax, by, bx, o, w, h))
+    csv_path = os.path.join(root, "DIW_test.csv")
+    with open(csv_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return csv_path
