@@ -358,6 +358,33 @@ int io_depth_errors_median(const float* pred, const uint16_t* gt, int B, int H, 
  * 0 otherwise (NaN).  Points are clamped into the h x w map. */
 int io_disp_sample_points(const float* disp, int B, int H, int W, const int* points, float* values, int* decisions,
                           hipStream_t stream);
+/* ---- mask relations and per-instance disparity statistics of one image (inference.py: bordering, select_pairs 'nbor',
+ * infer_gt_order, the area / y-axis baselines, net_forward_midas_pretrained) -------------------------------------------
+ * io_mask_pack: masks[n][H][W] (uint8) -> bits[n][H][ceil(W/32)] (uint32, pixel x of a row is bit x % 32 of word x / 32;
+ * bits past W are 0) of the predicate IO_MASK_NONZERO (m != 0) or IO_MASK_EQ1 (m == 1); with dilate != 0 a pixel is also
+ * set when one of its four cross neighbours inside the image satisfies the predicate (cv2.dilate with the 3x3 cross).
+ * stats (optional, int64 [n][4]): sum of m, #(m == 1), sum of the row index over m == 1, #(m != 0) -- exact.
+ * H * W < 2^31, n <= 65535.  No workspace. */
+#define IO_MASK_NONZERO 0
+#define IO_MASK_EQ1 1
+#define IO_MASK_MAX_N 65535
+int io_mask_pack(const uint8_t* masks, int n, int H, int W, int predicate, int dilate, uint32_t* bits, int64_t* stats,
+                 hipStream_t stream);
+/* io_mask_pair_counts: counts[i][j] (int32 [n_p][n_q]) = number of pixels set in both p_bits[i] and q_bits[j], bit images of
+ * io_mask_pack of the same H x W.  n_p, n_q <= IO_MASK_MAX_N, H * W < 2^31.  No workspace. */
+int io_mask_pair_counts(const uint32_t* p_bits, int n_p, const uint32_t* q_bits, int n_q, int H, int W, int32_t* counts,
+                        hipStream_t stream);
+/* io_instance_depth_select: per instance i of masks[n][H][W] (uint8) over one disparity map disp[H][W] (fp32), in fp32 as
+ * net_forward_midas_pretrained: V_i = 1 / (disp + 1e-6) where masks[i] != 0, k[i] = |V_i|, lo[i] / hi[i] =
+ * torch.quantile(V_i, 0.05 / 0.95) (linear rule, exact order statistics), value[i] = clamp(lower median of V_i, lo, hi)
+ * (IO_DEPTH_SELECT_MEDIAN, = torch.median of the clipped values) or the mean of clamp(V_i, lo, hi) (IO_DEPTH_SELECT_MEAN,
+ * fp64 sums in a fixed order).  k = 0 gives NaN.  lo, hi, k are optional.  Four launches (median) or six (mean) whatever
+ * n is; workspace: io_instance_depth_select_workspace_bytes(n, H, W) bytes. */
+#define IO_DEPTH_SELECT_MEAN 0
+#define IO_DEPTH_SELECT_MEDIAN 1
+size_t io_instance_depth_select_workspace_bytes(int n, int H, int W);
+int io_instance_depth_select(const float* disp, int H, int W, const uint8_t* masks, int n, int method, float* value, float* lo,
+                             float* hi, int32_t* k, void* workspace, size_t workspace_bytes, hipStream_t stream);
 /* io_conv2d_fwd_bnstats for either storage type and for the grouped window form (gw = 64; w = wc of io_gconv_pack,
  * Cin == Cout); gw = 0 is the dense convolution */
 int io_conv2d_fwd_bnstats_dt(const void* x, const void* w, void* y, int N, int H, int W, int Cin, int Cout, int R, int S,

@@ -180,6 +180,13 @@ SIGNATURES = {
     "io_depth_errors_median_workspace_bytes": (_Z, [_I, _I, _I]),
     "io_depth_errors_median": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "io_disp_sample_points": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    # masks (uint8), n, H, W, predicate, dilate, bits, stats, stream
+    "io_mask_pack": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    # p_bits, n_p, q_bits, n_q, H, W, counts, stream
+    "io_mask_pair_counts": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
+    "io_instance_depth_select_workspace_bytes": (_Z, [_I, _I, _I]),
+    # disp, H, W, masks, n, method, value, lo, hi, k, workspace, workspace_bytes, stream
+    "io_instance_depth_select": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "io_prof_begin": (_I, []),
     "io_prof_begin_ex": (_I, [_I]),
     "io_prof_end": (_I, [C.POINTER(ProfEntry), _I]),

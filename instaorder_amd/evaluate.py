@@ -57,12 +57,15 @@ def _gather_rows(rows, n_total, world_size):
 
 
 def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all", zd=0, disp_select_method="",
-             gt_ordering="ann", world_size=1, rank=0, return_orders=False):
+             gt_ordering="ann", world_size=1, rank=0, return_orders=False, mask_rules="host"):
     """Dispatch of ``Tester.run`` on ``data_cfg['trainval_dataset']``.  ``order_method``: one of the method strings of
     tools/test.py -- the network methods, or the annotation-free baselines 'area' / 'yaxis' (tools/test.py:306-318,
     421-433) -- or a callable ``(modal_masks, dataset_name) -> order matrix`` (any other model-free rule).  Returns a dict with 'recall', 'precision', 'f1'
     (occlusion datasets) and / or 'WHDR_<ovl>_<eq>' (depth datasets), plus 'num_test_images'; with ``return_orders``
-    also 'orders' = {image index: (occlusion matrix | None, depth matrix | None)} of this rank's images."""
+    also 'orders' = {image index: (occlusion matrix | None, depth matrix | None)} of this rank's images.
+    ``mask_rules='device'``: pair selection, the 'area' / 'yaxis' baselines, ``infer_gt_order`` and the disparity
+    selection run through ``instaorder_amd.mask_rules`` (same results); 'host' (the default) keeps the host loops."""
+    rules = infer._mask_rules(mask_rules) or infer          # the module whose mask rules this run uses
     kind = data_cfg["trainval_dataset"]
     want_occ = kind in ("SupOcclusionOrderDataset", "PartialCompDataset", "SupDepthOccOrderDataset")
     want_dep = kind in ("SupDepthOrderDataset", "SupDepthOccOrderDataset")
@@ -85,7 +88,7 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
             if dataset == "InstaOrder":
                 gt_occ = data_reader.get_gt_ordering(i, "occlusion", data_cfg["remove_occ_bidirec"])
             else:
-                gt_occ = data_reader.get_gt_ordering(i) if gt_ordering == "ann" else infer.infer_gt_order(modal, amodal_gt)
+                gt_occ = data_reader.get_gt_ordering(i) if gt_ordering == "ann" else rules.infer_gt_order(modal, amodal_gt)
         if want_dep:
             gt_dep = data_reader.get_gt_ordering(i, "depth", rm_overlap=0 if kind == "SupDepthOccOrderDataset"
                                                  else data_cfg["remove_depth_overlap"])
@@ -95,35 +98,36 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
                 raise Exception("No such order method: {}".format(order_method))
             if order_method == "InstaOrderNet_od":
                 pred_occ, pred_dep = infer.infer_order_sup_occ_depth(model, image, modal, boxes, pairs, order_method,
-                                                                     mode, size, disp_select_method)
+                                                                     mode, size, disp_select_method, mask_rules=mask_rules)
             else:
                 rgb, masks = infer.resize_mode_inputs(next(model.model.parameters()).device, image, modal, size) \
                     if mode == "resize" else _identity_inputs(image, modal, size)
-                res = infer.infer_depthnet_batched(model, rgb, masks, pairs=infer.select_pairs(modal, pairs))
+                res = infer.infer_depthnet_batched(model, rgb, masks, pairs=rules.select_pairs(modal, pairs))
                 pred_occ, pred_dep = res["occ_order"], res["depth_order"]
         elif want_dep:
             if callable(order_method):      # a device-free ordering rule: (modal masks, dataset name) -> matrix
                 pred_dep = order_method(modal, dataset)
             elif order_method == "area":    # tools/test.py:306-312: 'larger' for every dataset
-                pred_dep = infer.infer_depth_order_area(modal, closer="larger")
+                pred_dep = rules.infer_depth_order_area(modal, closer="larger")
             elif order_method == "yaxis":   # :314-318
-                pred_dep = infer.infer_depth_order_yaxis(modal, closer="lower" if dataset in ("COCOA", "InstaOrder")
+                pred_dep = rules.infer_depth_order_yaxis(modal, closer="lower" if dataset in ("COCOA", "InstaOrder")
                                                          else "higher")
             elif order_method in ("InstaOrderNet_d", "InstaDepthNet_d", "midas_pretrained"):
                 pred_dep, _ = infer.infer_order_sup_depth(model, image, modal, boxes, pairs, order_method, mode, size,
-                                                          disp_select_method)
+                                                          disp_select_method, mask_rules=mask_rules)
             else:
                 raise Exception("No such order method: {}".format(order_method))
         else:
             if callable(order_method):
                 pred_occ = order_method(modal, dataset)
             elif order_method == "area":    # tools/test.py:421-427
-                pred_occ = infer.infer_occ_order_area(modal, occluder="larger")
+                pred_occ = rules.infer_occ_order_area(modal, occluder="larger")
             elif order_method == "yaxis":   # :429-433
-                pred_occ = infer.infer_occ_order_yaxis(modal, occluder="lower" if dataset in ("COCOA", "InstaOrder")
+                pred_occ = rules.infer_occ_order_yaxis(modal, occluder="lower" if dataset in ("COCOA", "InstaOrder")
                                                        else "higher")
             elif order_method in ("InstaOrderNet_o", "OrderNet"):
-                pred_occ = infer.infer_order_sup_occ(model, image, modal, boxes, pairs, order_method, mode, size)
+                pred_occ = infer.infer_order_sup_occ(model, image, modal, boxes, pairs, order_method, mode, size,
+                                                     mask_rules=mask_rules)
             else:
                 raise Exception("No such order method: {}".format(order_method))
         row = []

@@ -374,8 +374,19 @@ def orig_mode_inputs(dev, image, inmodal):
     return _whole_image_inputs(dev, image, inmodal, (hh, ww))
 
 
-def _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size):
-    pair_list = select_pairs(inmodal, pairs)
+def _mask_rules(mask_rules):
+    """None for the host functions of this module, else the device module (``mask_rules='device'``)."""
+    from . import mask_rules as mr
+    return mr if mr.check_mode(mask_rules) else None
+
+
+def _select_pairs(mr, inmodal, pairs):
+    return mr.select_pairs(inmodal, pairs) if mr else select_pairs(inmodal, pairs)
+
+
+def _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size, mask_rules="host"):
+    mr = _mask_rules(mask_rules)
+    pair_list = _select_pairs(mr, inmodal, pairs)
     n = inmodal.shape[0]
     if not pair_list:
         z = np.zeros((n, n), dtype=np.int64)
@@ -390,16 +401,19 @@ def _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, inp
                                pair_planes=planes)
 
 
-def infer_order_sup_occ(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size=256, use_rgb=True):
+def infer_order_sup_occ(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size=256, use_rgb=True,
+                        mask_rules="host"):
     """Reference signature (inference.py:439-512): image uint8 [H,W,3], inmodal [N,H,W], bboxes [N,4] xywh; returns
-    the occlusion order matrix (1 at [i, j] = i occludes j)."""
-    return _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size)["occ_order"]
+    the occlusion order matrix (1 at [i, j] = i occludes j).  ``mask_rules='device'``: the 'nbor' pair selection runs
+    on the device (``mask_rules.select_pairs``)."""
+    return _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size, mask_rules)["occ_order"]
 
 
 def infer_order_sup_occ_depth(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size,
-                              disp_select_method=""):
-    """Reference signature (inference.py:349-436); returns (occ_order, depth_order)."""
-    res = _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size)
+                              disp_select_method="", mask_rules="host"):
+    """Reference signature (inference.py:349-436); returns (occ_order, depth_order).  ``mask_rules``: as
+    infer_order_sup_occ."""
+    res = _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size, mask_rules)
     return res["occ_order"], res["depth_order"]
 
 
@@ -483,12 +497,16 @@ def net_forward_midas_pretrained(pred_disp, inmodal1, inmodal2, disp_select_meth
 
 
 def infer_order_sup_depth(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size, disp_select_method,
-                          use_rgb=True):
+                          use_rgb=True, mask_rules="host"):
     """Reference signature (inference.py:515-625); returns (depth order matrix, clipped disparity | None).
     Methods: InstaOrderNet_d (the batched ResNet path) and InstaDepthNet_d / InstaDepthNet_od (batched MiDaS path;
-    with ``disp_select_method`` 'mean' / 'median' the order comes from the predicted disparity instead of the head)."""
+    with ``disp_select_method`` 'mean' / 'median' the order comes from the predicted disparity instead of the head).
+    ``mask_rules='device'``: pair selection and the per-pair disparity statistics run on the device
+    (``mask_rules.select_pairs`` / ``depth_orders_from_disp``); the masks of the 'resize' / 'orig' modes stay there."""
+    mr = _mask_rules(mask_rules)
     if method == "InstaOrderNet_d":
-        return _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size)["depth_order"], None
+        return _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size,
+                          mask_rules)["depth_order"], None
     if method == "midas_pretrained":
         # inference.py:583-590: `model` is the bare MidasNet; the order comes from its disparity under the two masks
         dev = next(model.parameters()).device
@@ -506,6 +524,8 @@ def infer_order_sup_depth(model, image, inmodal, bboxes, pairs, method, patch_or
         with torch.no_grad():
             disp = model(rgb.to(dev)).squeeze().float()
         clipped = torch.clip(disp, torch.quantile(disp, 0.05), torch.quantile(disp, 0.95))
+        if mr:
+            return mr.depth_orders_from_disp(disp, masks, mr.select_pairs(inmodal, pairs), disp_select_method), clipped
         masks_np = masks.cpu().numpy() if torch.is_tensor(masks) else masks
         n = inmodal.shape[0]
         order = np.zeros((n, n), dtype=np.int64)
@@ -521,27 +541,31 @@ def infer_order_sup_depth(model, image, inmodal, bboxes, pairs, method, patch_or
     if method not in ("InstaDepthNet_d", "InstaDepthNet_od"):
         raise ValueError("method name should be one of {InstaOrderNet_d, midas_pretrained, InstaDepthNet_d, InstaDepthNet_od}")
     # the batched MiDaS path runs the encoder once per IMAGE, which needs one image shared by all pairs
-    plist = select_pairs(inmodal, pairs)
+    plist = _select_pairs(mr, inmodal, pairs)
     if patch_or_image == "resize":              # what the reference's InstaDepthNet configs use (config.yaml:51)
         dev = next(model.model.parameters()).device
         rgb, masks = resize_mode_inputs(dev, image, inmodal, input_size)
-        rgb, masks = rgb.cpu().numpy(), masks.cpu().numpy()
+        if not mr:
+            rgb, masks = rgb.cpu().numpy(), masks.cpu().numpy()
     elif patch_or_image == "orig":              # the whole image at its own aspect ratio (inference.py:569-575)
         dev = next(model.model.parameters()).device
         rgb, masks = orig_mode_inputs(dev, image, inmodal)
-        rgb, masks = rgb.cpu().numpy(), masks.cpu().numpy()
+        if not mr:
+            rgb, masks = rgb.cpu().numpy(), masks.cpu().numpy()
     elif patch_or_image == "image" and image.shape[0] == image.shape[1] == input_size:
         from .synthetic import image_mode_inputs
         rgb, masks = image_mode_inputs(image, inmodal, input_size)
     else:
         raise NotImplementedError("InstaDepthNet inference: patch_or_image='resize' / 'orig', or 'image' on square images "
                                   "of the network size (per-pair crops would run the MiDaS encoder once per pair)")
-    res = infer_depthnet_batched(model, torch.from_numpy(rgb), torch.from_numpy(masks), pairs=plist)
+    res = infer_depthnet_batched(model, torch.as_tensor(rgb), torch.as_tensor(masks), pairs=plist)
     if disp_select_method == "":
         return res["depth_order"], None
     # the reference takes the disparity of a call with empty masks; the disparity does not depend on the masks
     disp = res["disp"]
     clipped = torch.clip(disp, torch.quantile(disp, 0.05), torch.quantile(disp, 0.95))
+    if mr:
+        return mr.depth_orders_from_disp(disp, masks, res["pairs"], disp_select_method), clipped
     n = masks.shape[0]
     order = np.zeros((n, n), dtype=np.int64)
     for i, j in res["pairs"]:
