@@ -699,8 +699,9 @@ extern "C" int io_colsum(const void* x, int M, int C, float* out, float* partial
                kThreads);
     int nb;
     const int rpb = rows_per_block(M, &nb);
-    IO_REQUIRE(partial_floats >= (size_t)nb * C, IO_ERR_WORKSPACE, "colsum: workspace %zu < %zu floats", partial_floats,
-               (size_t)nb * C);
+    // (the size io_colsum_partial_floats states, which io_head1_bwd shares: [nb][C + 1])
+    IO_REQUIRE(partial_floats >= (size_t)nb * (C + 1), IO_ERR_WORKSPACE, "colsum: workspace %zu < %zu floats", partial_floats,
+               (size_t)nb * (C + 1));
     IoProfScope prof(IO_PROF_BN_BWD, 0.0, (double)io_dtype_bytes(dt) * M * C, st);
     const int vec = 16 / io_dtype_bytes(dt);
     if (IO_HEAD_ROWS && C % vec == 0 && kThreads % (C / vec) == 0)
@@ -821,6 +822,18 @@ __device__ __forceinline__ SmoothNorm smooth_norm(const float* st, int N) {
 }
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
+// n(p) - n(q) of two normalised neighbours, n = (d - mn) * k.  No contraction: fused into the subtraction, na - (dq - mn) * k is
+// the rounding error of na -- not 0 -- for two EQUAL neighbours, and sgn() of it put a spurious +-e * cx into the gradient of
+// every tied pair (the plateaus of a ReLU head; tests/test_gpu_ext_edges.py::test_smooth_loss_tied_maps).
+__device__ __forceinline__ float smooth_nrm(float d, float mn, float k) {
+#pragma clang fp contract(off)
+    return (d - mn) * k;
+}
+__device__ __forceinline__ float smooth_diff(float na, float nb) {
+#pragma clang fp contract(off)
+    return na - nb;
+}
+
 // edge weight exp(-mean_c |img(c, p) - img(c, q)|) of the pixel pair (p, q), img NCHW with 3 channels
 __device__ __forceinline__ float edge_w(const float* img, int HW, int p, int q) {
     const float a = fabsf(img[p] - img[q]) + fabsf(img[HW + p] - img[HW + q]) + fabsf(img[2 * HW + p] - img[2 * HW + q]);
@@ -841,20 +854,20 @@ __global__ __launch_bounds__(kThreads) void smooth_fwd_kernel(const float* __res
     float lx = 0.f, ly = 0.f, a1 = 0.f, a2 = 0.f;
     for (int i = blockIdx.x * kThreads + threadIdx.x; i < N; i += gridDim.x * kThreads) {
         const int h = i / W, w = i - h * W;
-        const float n0 = (d[i] - q.mn) * k;
+        const float n0 = smooth_nrm(d[i], q.mn, k);
         float gi = 0.f;
         if (w + 1 < W) {
-            const float df = n0 - (d[i + 1] - q.mn) * k, e = edge_w(im, N, i, i + 1);
+            const float df = smooth_diff(n0, smooth_nrm(d[i + 1], q.mn, k)), e = edge_w(im, N, i, i + 1);
             lx += fabsf(df) * e;
             gi += sgn(df) * e * cx;
         }
-        if (w > 0) gi -= sgn((d[i - 1] - q.mn) * k - n0) * edge_w(im, N, i - 1, i) * cx;
+        if (w > 0) gi -= sgn(smooth_diff(smooth_nrm(d[i - 1], q.mn, k), n0)) * edge_w(im, N, i - 1, i) * cx;
         if (h + 1 < H) {
-            const float df = n0 - (d[i + W] - q.mn) * k, e = edge_w(im, N, i, i + W);
+            const float df = smooth_diff(n0, smooth_nrm(d[i + W], q.mn, k)), e = edge_w(im, N, i, i + W);
             ly += fabsf(df) * e;
             gi += sgn(df) * e * cy;
         }
-        if (h > 0) gi -= sgn((d[i - W] - q.mn) * k - n0) * edge_w(im, N, i - W, i) * cy;
+        if (h > 0) gi -= sgn(smooth_diff(smooth_nrm(d[i - W], q.mn, k), n0)) * edge_w(im, N, i - W, i) * cy;
         g[(size_t)b * N + i] = gi;
         a1 += gi;
         a2 += gi * n0;
@@ -917,7 +930,12 @@ __global__ __launch_bounds__(kThreads) void smooth_bwd_kernel(const float* __res
         if (key == kmn) v -= k * (a1 - a2);
         if (key == kmx) v -= q.s * a2 * kSmoothEps * q.r;
         float* o = ddisp + (size_t)b * N + i;
-        *o = accumulate ? *o + f * v : f * v;
+        {
+            // (no contraction: accumulate adds exactly the value the plain form stores)
+#pragma clang fp contract(off)
+            const float r = f * v;
+            *o = accumulate ? *o + r : r;
+        }
     }
 }
 
