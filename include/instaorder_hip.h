@@ -176,6 +176,45 @@ int io_adam_step(float* params, const float* grads, float* exp_avg, float* exp_a
                  double beta2, float eps, float weight_decay, double bias_correction1, double bias_correction2,
                  hipStream_t stream);
 
+/* ---- global-norm gradient clipping with a non-finite step guard (opt-in; the reference has none) ----
+ * io_grad_norm: sums of squares of the flat fp32 gradient buffer grads[n] in fp64 (each value is widened before it is
+ * squared: 1e-30 contributes 1e-60), per segment and in total.  seg_offsets: HOST array of nseg + 1 float offsets
+ * (1 <= nseg <= 16; multiples of 4, non-decreasing, first 0, last n; an empty segment is allowed); segment s is
+ * [seg_offsets[s], seg_offsets[s+1]).  Two launches whatever n is, no allocation, no synchronisation, no floating-point
+ * atomics: every block sums one fixed chunk of io_grad_norm_chunk_floats() floats of one segment into its slot of
+ * `workspace` (io_grad_norm_workspace_bytes(n, nseg) bytes, 8-byte aligned); one block then folds the slots of a segment
+ * in block order and the segments in segment order -- bitwise the same on every run for a given (n, seg_offsets).
+ * seg_sumsq: DEVICE double[nseg].  *state (DEVICE, zeroed once by the caller, then only handed back) receives
+ *   norm      = (float)sqrt(total)
+ *   coef      = min(1, max_norm / (norm + 1e-6f)) in fp32 with an IEEE division (torch.nn.utils.clip_grad_norm_'s
+ *               arithmetic; max_norm = +inf: exactly 1); max_norm must be > 0
+ *   nonfinite = !isfinite(norm): squares are non-negative, so an inf or NaN anywhere in grads reaches the total
+ *   steps / clipped / skipped: cumulative counts of calls, of calls with a finite norm and coef < 1, of calls with
+ *               nonfinite set.
+ * io_sgd_momentum_clipped / io_adam_step_clipped: io_sgd_momentum / io_adam_step with the record of the io_grad_norm
+ * call enqueued before them.  nonfinite set: nothing is written (parameters, momentum, both moments keep their bits).
+ * Otherwise the same update runs on g * coef, the product rounded to fp32 on its own: bitwise the unclipped call on a
+ * gradient buffer scaled by coef beforehand, and on the untouched gradients when coef is 1. */
+typedef struct io_clip_state {
+    float norm;
+    float coef;
+    int nonfinite;
+    int reserved0;
+    uint64_t steps;
+    uint64_t clipped;
+    uint64_t skipped;
+    uint64_t reserved[3];      /* pads the record to 64 bytes */
+} io_clip_state;
+int io_grad_norm_chunk_floats(void);
+size_t io_grad_norm_workspace_bytes(size_t n, int nseg);
+int io_grad_norm(const float* grads, size_t n, const size_t* seg_offsets, int nseg, float max_norm, void* workspace,
+                 size_t workspace_bytes, double* seg_sumsq, io_clip_state* state, hipStream_t stream);
+int io_sgd_momentum_clipped(float* params, const float* grads, float* momentum_buf, size_t n, float lr, float momentum,
+                            float weight_decay, const io_clip_state* clip, hipStream_t stream);
+int io_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                         double beta1, double beta2, float eps, float weight_decay, double bias_correction1,
+                         double bias_correction2, const io_clip_state* clip, hipStream_t stream);
+
 /* ---- whole-network executor: resnet50_cls(in_channels=5, num_classes=K | [K0,K1])
  * (resnet_cls.py:259-268) forward / backward over caller-owned flat buffers. ----------------- */
 typedef struct io_net io_net;

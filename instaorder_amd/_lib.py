@@ -53,6 +53,12 @@ class ProfEntry(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double), ("flops_executed", C.c_double)]
 
 
+class ClipState(C.Structure):
+    """io_clip_state of include/instaorder_hip.h: the 64-byte device record io_grad_norm leaves for the clipped updates"""
+    _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("nonfinite", C.c_int), ("reserved0", C.c_int),
+                ("steps", C.c_uint64), ("clipped", C.c_uint64), ("skipped", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 _D = C.c_double
 
@@ -95,6 +101,13 @@ SIGNATURES = {
     "io_sgd_momentum": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P]),
     # params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, stream
     "io_adam_step": (_I, [_P, _P, _P, _P, _Z, _D, _D, _D, _F, _F, _D, _D, _P]),
+    # grads, n, seg_offsets (host size_t[nseg + 1]), nseg, max_norm, workspace, workspace_bytes, seg_sumsq, state, stream
+    "io_grad_norm": (_I, [_P, _Z, C.POINTER(C.c_size_t), _I, _F, _P, _Z, _P, _P, _P]),
+    "io_grad_norm_workspace_bytes": (_Z, [_Z, _I]),
+    "io_grad_norm_chunk_floats": (_I, []),
+    # io_sgd_momentum / io_adam_step with the io_clip_state record in front of the stream
+    "io_sgd_momentum_clipped": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P, _P]),
+    "io_adam_step_clipped": (_I, [_P, _P, _P, _P, _Z, _D, _D, _D, _F, _F, _D, _D, _P, _P]),
     "io_net_create": (_P, [_I, _I, C.POINTER(C.c_int)]),
     "io_net_destroy": (None, [_P]),
     "io_net_param_floats": (_L, [_P]),

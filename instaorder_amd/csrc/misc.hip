@@ -1,5 +1,5 @@
 // Small HBM-bound / latency-bound kernels of the order-prediction path: input packing, max-pool,
-// global-average-pool + FC heads, order losses, momentum SGD, Adam, filter transposition.
+// global-average-pool + FC heads, order losses, momentum SGD, Adam, the gradient norm, filter transposition.
 #include "io_common.h"
 
 #ifndef IO_POOL_ROWS
@@ -486,46 +486,163 @@ __global__ __launch_bounds__(kThreads) void order_loss_kernel(const float* __res
 
 // ---- momentum SGD over the flat parameter buffer (single_stage_model.py:35-38) -------------------
 // d = g + wd*p ; buf = momentum*buf + d ; p -= lr*buf      (buf starts at 0 == "first step buf=d")
+__device__ __forceinline__ void sgd_update4(float* __restrict__ p, const f32x4 gv, float* __restrict__ buf, size_t i,
+                                            float lr, float momentum, float wd) {
+    const f32x4 pv = ld4(p + i * 4);
+    const f32x4 d = gv + wd * pv;
+    const f32x4 b = momentum * ld4(buf + i * 4) + d;
+    st4(buf + i * 4, b);
+    st4(p + i * 4, pv - lr * b);
+}
+
 __global__ __launch_bounds__(kThreads) void sgd_momentum_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                                float* __restrict__ buf, size_t n4, float lr,
                                                                float momentum, float wd) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const f32x4 pv = ld4(p + i * 4);
-        const f32x4 d = ld4(g + i * 4) + wd * pv;
-        const f32x4 b = momentum * ld4(buf + i * 4) + d;
-        st4(buf + i * 4, b);
-        st4(p + i * 4, pv - lr * b);
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
+        sgd_update4(p, ld4(g + i * 4), buf, i, lr, momentum, wd);
+}
+
+// ---- gradient clipping (io_grad_norm's record): the update above on gc = g * coef, or nothing at all ---------------
+// gc is rounded to fp32 on its own (__fmul_rn: never contracted into the update's first multiply-add), so the result is
+// bitwise the plain kernel's on a gradient buffer scaled beforehand; coef == 1 leaves every finite g as it is.  A
+// non-finite norm ends every thread before its first store: parameters and optimiser state keep their bits.
+__device__ __forceinline__ f32x4 clip_scale4(const f32x4 g, float coef) {
+    f32x4 r;
+    r.x = __fmul_rn(g.x, coef);
+    r.y = __fmul_rn(g.y, coef);
+    r.z = __fmul_rn(g.z, coef);
+    r.w = __fmul_rn(g.w, coef);
+    return r;
+}
+
+__global__ __launch_bounds__(kThreads) void sgd_momentum_clipped_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                       float* __restrict__ buf, size_t n4, float lr,
+                                                                       float momentum, float wd,
+                                                                       const io_clip_state* __restrict__ clip) {
+    if (clip->nonfinite) return;
+    const float coef = clip->coef;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
+        sgd_update4(p, clip_scale4(ld4(g + i * 4), coef), buf, i, lr, momentum, wd);
 }
 
 // ---- Adam over the flat parameter buffer (single_stage_model.py:39-42: torch.optim.Adam, amsgrad off) ------------
 // torch's single-tensor Adam, in its order: g += wd*p (coupled L2, wd != 0 only) ; m = lerp(m, g, 1-b1) ;
 // v = b2*v + (1-b2)*g*g ; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps), step_size = lr/bc1.  lerp as torch evaluates
 // it: weight < 0.5 -> m + w*(g-m), else g - (g-m)*(1-w).  28 B of HBM traffic per element.
+struct AdamArgs {
+    float w1, b2, omb2, eps, wd, step_size, bc2_sqrt;
+};
+
+__device__ __forceinline__ void adam_update4(float* __restrict__ p, f32x4 gv, float* __restrict__ m, float* __restrict__ v,
+                                             size_t i, const AdamArgs& a, bool small_w, float omw1) {
+    const f32x4 pv = ld4(p + i * 4);
+    if (a.wd != 0.f) gv = gv + a.wd * pv;
+    const f32x4 mv = ld4(m + i * 4);
+    const f32x4 d = gv - mv;
+    const f32x4 mn = small_w ? mv + a.w1 * d : gv - d * omw1;
+    const f32x4 vn = a.b2 * ld4(v + i * 4) + a.omb2 * gv * gv;
+    f32x4 den;
+    den.x = sqrtf(vn.x) / a.bc2_sqrt + a.eps;
+    den.y = sqrtf(vn.y) / a.bc2_sqrt + a.eps;
+    den.z = sqrtf(vn.z) / a.bc2_sqrt + a.eps;
+    den.w = sqrtf(vn.w) / a.bc2_sqrt + a.eps;
+    st4(m + i * 4, mn);
+    st4(v + i * 4, vn);
+    st4(p + i * 4, pv - a.step_size * (mn / den));
+}
+
 __global__ __launch_bounds__(kThreads) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v, size_t n4, float w1,
-                                                       float b2, float omb2, float eps, float wd, float step_size,
-                                                       float bc2_sqrt) {
+                                                       float* __restrict__ m, float* __restrict__ v, size_t n4, AdamArgs a) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const bool small_w = w1 < 0.5f;
-    const float omw1 = 1.f - w1;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const f32x4 pv = ld4(p + i * 4);
-        f32x4 gv = ld4(g + i * 4);
-        if (wd != 0.f) gv = gv + wd * pv;
-        const f32x4 mv = ld4(m + i * 4);
-        const f32x4 d = gv - mv;
-        const f32x4 mn = small_w ? mv + w1 * d : gv - d * omw1;
-        const f32x4 vn = b2 * ld4(v + i * 4) + omb2 * gv * gv;
-        f32x4 den;
-        den.x = sqrtf(vn.x) / bc2_sqrt + eps;
-        den.y = sqrtf(vn.y) / bc2_sqrt + eps;
-        den.z = sqrtf(vn.z) / bc2_sqrt + eps;
-        den.w = sqrtf(vn.w) / bc2_sqrt + eps;
-        st4(m + i * 4, mn);
-        st4(v + i * 4, vn);
-        st4(p + i * 4, pv - step_size * (mn / den));
+    const bool small_w = a.w1 < 0.5f;
+    const float omw1 = 1.f - a.w1;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
+        adam_update4(p, ld4(g + i * 4), m, v, i, a, small_w, omw1);
+}
+
+__global__ __launch_bounds__(kThreads) void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v, size_t n4,
+                                                               AdamArgs a, const io_clip_state* __restrict__ clip) {
+    if (clip->nonfinite) return;
+    const float coef = clip->coef;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const bool small_w = a.w1 < 0.5f;
+    const float omw1 = 1.f - a.w1;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
+        adam_update4(p, clip_scale4(ld4(g + i * 4), coef), m, v, i, a, small_w, omw1);
+}
+
+// ---- global gradient norm over the flat gradient buffer, per segment and in total (io_grad_norm) -------------------
+// Every block owns one fixed chunk (kNormChunk floats, the last chunk of a segment shorter) of ONE segment: 16-byte loads,
+// each value widened to double BEFORE it is squared (1e-30 contributes 1e-60, not 0; 1e30 does not overflow), a fixed
+// shuffle / LDS tree, one fp64 partial per block in the caller's slab.  grad_norm_fold_kernel (one block) then folds the
+// partials of a segment in block order and the segments in segment order and leaves the io_clip_state record.  No atomics:
+// for a given (n, segments) the summation tree is fixed, so the result is bitwise the same on every run.
+constexpr int kNormChunk = 16384;                     // floats per block: 16 sixteen-byte loads per thread
+constexpr int kNormMaxSeg = 16;
+struct NormTable {
+    int nseg;
+    int start[kNormMaxSeg + 1];                       // first block of segment s (start[nseg] = grid size)
+    unsigned long long off[kNormMaxSeg + 1];          // float offsets, multiples of 4, non-decreasing
+};
+
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < kThreads / 64; ++w) s += red[w];
+    __syncthreads();
+    return s;                                         // valid in thread 0
+}
+
+__global__ __launch_bounds__(kThreads) void grad_norm_partial_kernel(NormTable tab, const float* __restrict__ g,
+                                                                    double* __restrict__ partial) {
+    __shared__ double red[kThreads / 64];
+    int s = 0;
+    while (s + 1 < tab.nseg && (int)blockIdx.x >= tab.start[s + 1]) ++s;
+    const size_t lo = tab.off[s] + (size_t)((int)blockIdx.x - tab.start[s]) * kNormChunk;
+    const size_t seg_hi = tab.off[s + 1];
+    const size_t hi = lo + kNormChunk < seg_hi ? lo + kNormChunk : seg_hi;
+    double acc = 0.0;
+#pragma unroll 4
+    for (size_t i = lo + (size_t)threadIdx.x * 4; i < hi; i += (size_t)kThreads * 4) {
+        const f32x4 x = ld4(g + i);
+        const double a = x.x, b = x.y, c = x.z, d = x.w;
+        acc += (a * a + b * b) + (c * c + d * d);
+    }
+    const double tot = block_sum_f64(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kThreads) void grad_norm_fold_kernel(NormTable tab, const double* __restrict__ partial,
+                                                                 double* __restrict__ seg_sumsq, float max_norm,
+                                                                 io_clip_state* __restrict__ state) {
+    __shared__ double red[kThreads / 64];
+    double total = 0.0;
+    for (int s = 0; s < tab.nseg; ++s) {
+        double acc = 0.0;
+        for (int b = tab.start[s] + (int)threadIdx.x; b < tab.start[s + 1]; b += kThreads) acc += partial[b];
+        const double seg = block_sum_f64(acc, red);
+        if (threadIdx.x == 0) {
+            seg_sumsq[s] = seg;
+            total += seg;
+        }
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(total);
+        // torch.nn.utils.clip_grad_norm_'s arithmetic: max_norm / (norm + 1e-6) clamped to 1, in fp32, IEEE division
+        const float coef = fminf(1.f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f)));
+        const int bad = !isfinite(norm);
+        state->norm = norm;
+        state->coef = coef;
+        state->nonfinite = bad;
+        state->steps += 1;
+        state->clipped += (!bad && coef < 1.f) ? 1 : 0;
+        state->skipped += bad ? 1 : 0;
     }
 }
 
@@ -748,31 +865,124 @@ extern "C" int io_order_loss(const float* logits, int N, int B, int Kocc, int Kd
     return io_check_launch("order_loss");
 }
 
-extern "C" int io_sgd_momentum(float* params, const float* grads, float* momentum_buf, size_t n, float lr,
-                               float momentum, float weight_decay, hipStream_t st) {
+static int sgd_launch(float* params, const float* grads, float* momentum_buf, size_t n, float lr, float momentum,
+                      float weight_decay, const io_clip_state* clip, bool clipped, hipStream_t st) {
     IO_REQUIRE(n % 4 == 0, IO_ERR_SHAPE, "sgd: n=%zu must be a multiple of 4", n);
+    IO_REQUIRE(!clipped || clip, IO_ERR_SHAPE, "sgd: the clipped step needs the io_clip_state record of io_grad_norm");
     const size_t n4 = n / 4;
     IoProfScope prof(IO_PROF_SGD, 0.0, 20.0 * n, st);
-    hipLaunchKernelGGL(sgd_momentum_kernel, dim3(ew_blocks(n4)), dim3(kThreads), 0, st, params, grads, momentum_buf,
-                       n4, lr, momentum, weight_decay);
+    if (clipped)
+        hipLaunchKernelGGL(sgd_momentum_clipped_kernel, dim3(ew_blocks(n4)), dim3(kThreads), 0, st, params, grads,
+                           momentum_buf, n4, lr, momentum, weight_decay, clip);
+    else
+        hipLaunchKernelGGL(sgd_momentum_kernel, dim3(ew_blocks(n4)), dim3(kThreads), 0, st, params, grads, momentum_buf,
+                           n4, lr, momentum, weight_decay);
     return io_check_launch("sgd_momentum");
+}
+
+extern "C" int io_sgd_momentum(float* params, const float* grads, float* momentum_buf, size_t n, float lr,
+                               float momentum, float weight_decay, hipStream_t st) {
+    return sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, nullptr, false, st);
+}
+
+extern "C" int io_sgd_momentum_clipped(float* params, const float* grads, float* momentum_buf, size_t n, float lr,
+                                       float momentum, float weight_decay, const io_clip_state* clip, hipStream_t st) {
+    return sgd_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, clip, true, st);
+}
+
+static int adam_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
+                       double beta1, double beta2, float eps, float weight_decay, double bias_correction1,
+                       double bias_correction2, const io_clip_state* clip, bool clipped, hipStream_t st) {
+    IO_REQUIRE(n % 4 == 0, IO_ERR_SHAPE, "adam: n=%zu must be a multiple of 4", n);
+    IO_REQUIRE(bias_correction1 > 0.0 && bias_correction2 > 0.0, IO_ERR_SHAPE, "adam: bias corrections %g %g must be > 0",
+               bias_correction1, bias_correction2);
+    IO_REQUIRE(!clipped || clip, IO_ERR_SHAPE, "adam: the clipped step needs the io_clip_state record of io_grad_norm");
+    const size_t n4 = n / 4;
+    // as torch: 1 - beta, lr / bc1 and sqrt(bc2) in double, each rounded to fp32 once
+    AdamArgs a;
+    a.w1 = (float)(1.0 - beta1);
+    a.b2 = (float)beta2;
+    a.omb2 = (float)(1.0 - beta2);
+    a.eps = eps;
+    a.wd = weight_decay;
+    a.step_size = (float)(lr / bias_correction1);
+    a.bc2_sqrt = (float)sqrt(bias_correction2);
+    IoProfScope prof(IO_PROF_ADAM, 0.0, 28.0 * n, st);
+    if (n4 == 0) return IO_OK;
+    if (clipped)
+        hipLaunchKernelGGL(adam_clipped_kernel, dim3(ew_blocks(n4)), dim3(kThreads), 0, st, params, grads, exp_avg,
+                           exp_avg_sq, n4, a, clip);
+    else
+        hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n4)), dim3(kThreads), 0, st, params, grads, exp_avg, exp_avg_sq, n4,
+                           a);
+    return io_check_launch("adam");
 }
 
 extern "C" int io_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, double lr,
                             double beta1, double beta2, float eps, float weight_decay, double bias_correction1,
                             double bias_correction2, hipStream_t st) {
-    IO_REQUIRE(n % 4 == 0, IO_ERR_SHAPE, "adam: n=%zu must be a multiple of 4", n);
-    IO_REQUIRE(bias_correction1 > 0.0 && bias_correction2 > 0.0, IO_ERR_SHAPE, "adam: bias corrections %g %g must be > 0",
-               bias_correction1, bias_correction2);
-    const size_t n4 = n / 4;
-    // as torch: 1 - beta, lr / bc1 and sqrt(bc2) in double, each rounded to fp32 once
-    const float step_size = (float)(lr / bias_correction1);
-    const float bc2_sqrt = (float)sqrt(bias_correction2);
-    IoProfScope prof(IO_PROF_ADAM, 0.0, 28.0 * n, st);
-    if (n4 == 0) return IO_OK;
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n4)), dim3(kThreads), 0, st, params, grads, exp_avg, exp_avg_sq, n4,
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, weight_decay, step_size, bc2_sqrt);
-    return io_check_launch("adam");
+    return adam_launch(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                       bias_correction2, nullptr, false, st);
+}
+
+extern "C" int io_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n,
+                                    double lr, double beta1, double beta2, float eps, float weight_decay,
+                                    double bias_correction1, double bias_correction2, const io_clip_state* clip,
+                                    hipStream_t st) {
+    return adam_launch(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                       bias_correction2, clip, true, st);
+}
+
+// ---- io_grad_norm: the host side lays the blocks out over the segments; the table rides in the kernel arguments ------
+static int norm_table(NormTable& tab, size_t n, const size_t* seg_offsets, int nseg) {
+    IO_REQUIRE(seg_offsets && nseg >= 1 && nseg <= kNormMaxSeg, IO_ERR_SHAPE, "grad_norm: nseg=%d must be 1..%d", nseg,
+               kNormMaxSeg);
+    IO_REQUIRE(seg_offsets[0] == 0 && seg_offsets[nseg] == n, IO_ERR_SHAPE,
+               "grad_norm: the segments must cover [0, n=%zu) (first offset %zu, last %zu)", n, seg_offsets[0],
+               seg_offsets[nseg]);
+    tab.nseg = nseg;
+    tab.start[0] = 0;
+    for (int s = 0; s <= nseg; ++s) {
+        IO_REQUIRE(seg_offsets[s] % 4 == 0 && (s == 0 || seg_offsets[s] >= seg_offsets[s - 1]), IO_ERR_SHAPE,
+                   "grad_norm: offset %d (%zu) must be a multiple of 4 and not below its predecessor", s, seg_offsets[s]);
+        tab.off[s] = seg_offsets[s];
+        if (s > 0) {
+            const size_t blocks = (seg_offsets[s] - seg_offsets[s - 1] + kNormChunk - 1) / kNormChunk;
+            IO_REQUIRE(tab.start[s - 1] + blocks < (1ull << 31), IO_ERR_SHAPE, "grad_norm: n=%zu is too large", n);
+            tab.start[s] = tab.start[s - 1] + (int)blocks;
+        }
+    }
+    return IO_OK;
+}
+
+extern "C" int io_grad_norm_chunk_floats(void) { return kNormChunk; }
+
+extern "C" size_t io_grad_norm_workspace_bytes(size_t n, int nseg) {
+    // every segment ends in at most one partial chunk
+    return ((n + kNormChunk - 1) / kNormChunk + (size_t)(nseg > 0 ? nseg : 0)) * sizeof(double);
+}
+
+extern "C" int io_grad_norm(const float* grads, size_t n, const size_t* seg_offsets, int nseg, float max_norm,
+                            void* workspace, size_t workspace_bytes, double* seg_sumsq, io_clip_state* state,
+                            hipStream_t st) {
+    static_assert(sizeof(io_clip_state) == 64, "io_clip_state is a 64-byte record");
+    NormTable tab;
+    const int rc = norm_table(tab, n, seg_offsets, nseg);
+    if (rc != IO_OK) return rc;
+    IO_REQUIRE(max_norm > 0.f, IO_ERR_SHAPE, "grad_norm: max_norm=%g must be > 0 (+inf: measure only)", (double)max_norm);
+    IO_REQUIRE(seg_sumsq && state && (grads || n == 0), IO_ERR_SHAPE, "grad_norm: null pointer");
+    const size_t blocks = (size_t)tab.start[nseg];
+    IO_REQUIRE(blocks == 0 || (workspace && workspace_bytes >= blocks * sizeof(double)), IO_ERR_SHAPE,
+               "grad_norm: workspace of %zu bytes, %zu needed", workspace_bytes, blocks * sizeof(double));
+    IO_REQUIRE(((uintptr_t)grads & 15) == 0 && ((uintptr_t)workspace & 7) == 0, IO_ERR_SHAPE,
+               "grad_norm: grads must be 16-byte aligned, the workspace 8-byte aligned");
+    IoProfScope prof(IO_PROF_GRAD_NORM, 3.0 * n, 4.0 * n, st);
+    if (blocks)
+        hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, tab, grads,
+                           (double*)workspace);
+    hipLaunchKernelGGL(grad_norm_fold_kernel, dim3(1), dim3(kThreads), 0, st, tab, (const double*)workspace, seg_sumsq,
+                       max_norm, state);
+    return io_check_launch("grad_norm");
 }
 
 int io_filter_prepare_t(const float* w, int O, int T, int C, void* dst, int transpose, hipStream_t st, int dt) {

@@ -174,15 +174,24 @@ def order_loss(logits, B, Kocc, Kdep, occ_target=None, depth_target=None, is_ove
     return losses, dlogits
 
 
-def sgd_momentum(params, grads, buf, lr, momentum, weight_decay):
+def sgd_momentum(params, grads, buf, lr, momentum, weight_decay, clip_state=None):
+    """clip_state: the record of the grad_norm() call enqueued before this one -- the update runs on grads * coef, or
+    not at all when the norm was not finite (io_sgd_momentum_clipped); None: the plain update."""
     _lib.require_gpu()
-    _lib.check(_lib.lib().io_sgd_momentum(_ptr(params), _ptr(grads), _ptr(buf), params.numel(), float(lr),
-                                          float(momentum), float(weight_decay), _stream()), "io_sgd_momentum")
+    if clip_state is None:
+        _lib.check(_lib.lib().io_sgd_momentum(_ptr(params), _ptr(grads), _ptr(buf), params.numel(), float(lr),
+                                              float(momentum), float(weight_decay), _stream()), "io_sgd_momentum")
+    else:
+        _lib.check(_lib.lib().io_sgd_momentum_clipped(_ptr(params), _ptr(grads), _ptr(buf), params.numel(), float(lr),
+                                                      float(momentum), float(weight_decay), _ptr(_clip_record(clip_state)),
+                                                      _stream()), "io_sgd_momentum_clipped")
 
 
-def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, begin=0, end=None):
+def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, begin=0, end=None,
+              clip_state=None):
     """torch.optim.Adam's update of the elements [begin, end) of the flat fp32 buffers, all at step count ``step``
-    (>= 1, the count after this update); the bias corrections are computed here in double, as torch does."""
+    (>= 1, the count after this update); the bias corrections are computed here in double, as torch does.  clip_state: as
+    in sgd_momentum (io_adam_step_clipped)."""
     _lib.require_gpu()
     end = params.numel() if end is None else end
     for t in (grads, exp_avg, exp_avg_sq):
@@ -194,9 +203,74 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_
 
     def at(t):
         return C.c_void_p(t.data_ptr() + 4 * begin)
-    _lib.check(_lib.lib().io_adam_step(at(params), at(grads), at(exp_avg), at(exp_avg_sq), end - begin, float(lr),
-                                       float(beta1), float(beta2), float(eps), float(weight_decay), bc1, bc2, _stream()),
-                                       "io_adam_step")
+    if clip_state is None:
+        _lib.check(_lib.lib().io_adam_step(at(params), at(grads), at(exp_avg), at(exp_avg_sq), end - begin, float(lr),
+                                           float(beta1), float(beta2), float(eps), float(weight_decay), bc1, bc2, _stream()),
+                                           "io_adam_step")
+    else:
+        _lib.check(_lib.lib().io_adam_step_clipped(at(params), at(grads), at(exp_avg), at(exp_avg_sq), end - begin,
+                                                   float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                                   bc1, bc2, _ptr(_clip_record(clip_state)), _stream()),
+                   "io_adam_step_clipped")
+
+
+# ---- global gradient norm / clipping record (io_grad_norm) ---------------------------------------------------------
+CLIP_STATE_BYTES = C.sizeof(_lib.ClipState)          # 64
+
+
+def _clip_record(t):
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == CLIP_STATE_BYTES):
+        raise ValueError("clip_state must be the %d-byte uint8 device record of new_clip_state()" % CLIP_STATE_BYTES)
+    return t
+
+
+def new_clip_state(device):
+    """A zeroed io_clip_state record on ``device`` (a uint8 tensor of 64 bytes; read_clip_state decodes it)."""
+    return torch.zeros(CLIP_STATE_BYTES, dtype=torch.uint8, device=device)
+
+
+def read_clip_state(state):
+    """The record as a dict (synchronises: one 64-byte copy to the host)."""
+    raw = _lib.ClipState.from_buffer_copy(bytes(state.cpu().numpy().tobytes()))
+    return dict(norm=float(raw.norm), coef=float(raw.coef), nonfinite=int(raw.nonfinite),
+                steps=int(raw.steps), clipped=int(raw.clipped), skipped=int(raw.skipped))
+
+
+def grad_norm_chunk():
+    """floats one block of io_grad_norm sums"""
+    return int(_lib.lib().io_grad_norm_chunk_floats())
+
+
+def grad_norm_workspace_bytes(n, nseg=1):
+    return int(_lib.lib().io_grad_norm_workspace_bytes(int(n), int(nseg)))
+
+
+def grad_norm(grads, max_norm, state, seg_offsets=None, workspace=None, seg_sumsq=None):
+    """Sum of squares of the flat fp32 buffer ``grads`` in fp64, per segment (``seg_offsets``: nseg + 1 increasing float
+    offsets from 0 to grads.numel(), multiples of 4; None: one segment) and in total, and the clipping record for
+    ``max_norm`` (> 0; inf: measure only) in ``state`` (new_clip_state).  Two launches, nothing allocated when
+    ``workspace`` (uint8, grad_norm_workspace_bytes) and ``seg_sumsq`` (float64[nseg]) are given -- capturable.  Returns
+    seg_sumsq (device float64)."""
+    _lib.require_gpu()
+    _dev_f32(grads, "grads")
+    n = grads.numel()
+    offs = [0, n] if seg_offsets is None else [int(o) for o in seg_offsets]
+    nseg = len(offs) - 1
+    need = grad_norm_workspace_bytes(n, nseg)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=grads.device)
+    if seg_sumsq is None:
+        seg_sumsq = torch.empty(max(nseg, 1), dtype=torch.float64, device=grads.device)
+    if not (seg_sumsq.is_cuda and seg_sumsq.dtype == torch.float64 and seg_sumsq.is_contiguous()
+            and seg_sumsq.numel() >= nseg):
+        raise ValueError("seg_sumsq must be a contiguous float64 device tensor of at least %d elements" % nseg)
+    if not (workspace.is_cuda and workspace.is_contiguous()):
+        raise ValueError("workspace must be a contiguous device tensor")
+    arr = (C.c_size_t * len(offs))(*offs)
+    _lib.check(_lib.lib().io_grad_norm(_ptr(grads), n, arr, nseg, float(max_norm), _ptr(workspace),
+                                       workspace.numel() * workspace.element_size(), _ptr(seg_sumsq),
+                                       _ptr(_clip_record(state)), _stream()), "io_grad_norm")
+    return seg_sumsq
 
 
 _prof_on = False

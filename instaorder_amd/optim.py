@@ -11,14 +11,117 @@ a ``torch.optim.Optimizer`` (utils/scheduler.py:7-9 type-checks it and rewrites
 FusedAdam / FlatAdam do the same for ``optim: Adam`` (single_stage_model.py:39-42, torch.optim.Adam with
 betas=(beta1, 0.999)) over the same two flat layouts: torch.optim.Adam's state_dict layout, per-parameter step counts,
 parameters without a gradient skipped as torch skips them.
+
+All four take ``max_grad_norm`` (default None: off, everything as without it): global-norm gradient clipping with a
+non-finite step guard (_GradClip below; DESIGN.md "Gradient clipping and the non-finite guard").
 """
+import math
+
 import torch
 
 from . import engine
 
 
-class FusedSGD(torch.optim.Optimizer):
-    def __init__(self, module, lr, momentum=0.9, weight_decay=0.0):
+def _check_max_grad_norm(v):
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or not v > 0:
+        raise ValueError("max_grad_norm must be a positive number or float('inf') (None: no clipping), got %r" % (v,))
+    return float(v)
+
+
+class _GradClip(object):
+    """Global-norm clipping of the flat gradient buffer and the non-finite guard, mixed into the four flat optimisers.
+
+    With ``max_grad_norm`` set, ``step()`` first runs io_grad_norm over ``flat_grads`` (fp64 sums of squares per segment
+    and in total, two launches, no host synchronisation) and then the clipped update, which reads the device record
+    io_grad_norm left: gradients scaled by coef = min(1, max_grad_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s
+    arithmetic -- or, when the norm is inf / NaN, NO update at all (parameters and optimiser state keep their bits, the
+    record's ``skipped`` count goes up).  ``float('inf')`` measures and guards without ever scaling.
+
+    ``step()`` is what the model wrappers call AFTER the data-parallel gradient exchange (every path of _OrderBase.step /
+    _DepthBase.step, the staged ones after their last bucket has arrived), so the clip acts on the summed gradient, the
+    same on every rank.  The norm is defined over parameter elements: the storage padding of the flat buffers (the stem
+    filter's channels 5..7, the 64-float span padding of _FlatLayout) holds zero gradients and contributes nothing.
+
+    The setting is an attribute, not a param-group key: state_dict() stays in torch's layout and checkpoints written with
+    and without clipping interchange.  Known limit: on a skipped step Adam's host-side per-parameter step counts still
+    advance (keeping them would need a host synchronisation); moments and parameters do not change."""
+
+    def _clip_init(self, max_grad_norm):
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self._seg_names = ("all",)
+        self._seg_offsets = None        # None: one segment over the whole buffer
+        self._clip_bufs = None          # (state record, fp64 segment sums, workspace)
+
+    def set_grad_segments(self, slices, names=None):
+        """``slices``: [lo, hi) float ranges that tile the flat gradient buffer (any order, e.g. the backward stages of
+        grad_stage_slices(); at most 16, boundaries multiples of 4); grad_stats() reports one norm per range under
+        ``names``."""
+        slices = [(int(lo), int(hi)) for lo, hi in slices]
+        names = tuple(names) if names is not None else tuple("stage%d" % i for i in range(len(slices)))
+        if not 1 <= len(slices) <= 16 or len(names) != len(slices) or len(set(names)) != len(names):
+            raise ValueError("gradient segments: 1..16 ranges with one distinct name each")
+        order = sorted(range(len(slices)), key=lambda i: slices[i])
+        offs = [slices[order[0]][0]]
+        for i in order:
+            lo, hi = slices[i]
+            if lo != offs[-1] or hi < lo or lo % 4 or hi % 4:
+                raise ValueError("gradient segments must tile the buffer with boundaries that are multiples of 4: %r"
+                                 % (slices,))
+            offs.append(hi)
+        if offs[0] != 0:
+            raise ValueError("gradient segments must start at 0: %r" % (slices,))
+        self._seg_offsets = offs
+        self._seg_names = tuple(names[i] for i in order)
+        self._clip_bufs = None
+
+    def _clip_buffers(self, flat_grads):
+        n = flat_grads.numel()
+        offs = self._seg_offsets if self._seg_offsets is not None else [0, n]
+        if offs[-1] != n:
+            raise ValueError("gradient segments end at %d, the flat gradient buffer has %d floats" % (offs[-1], n))
+        b = self._clip_bufs
+        if b is None or b[0].device != flat_grads.device:
+            dev = flat_grads.device
+            state = engine.new_clip_state(dev)
+            if b is not None:
+                state.copy_(b[0])       # the counters move with the model
+            b = (state, torch.zeros(len(offs) - 1, dtype=torch.float64, device=dev),
+                 torch.empty(max(8, engine.grad_norm_workspace_bytes(n, len(offs) - 1)), dtype=torch.uint8, device=dev))
+            self._clip_bufs = b
+        return offs, b
+
+    def _measure(self, flat_grads):
+        """io_grad_norm over the flat gradients when clipping is on; returns the device record (None: clipping off)"""
+        max_norm = _check_max_grad_norm(getattr(self, "max_grad_norm", None))
+        if max_norm is None:
+            return None
+        offs, (state, seg, ws) = self._clip_buffers(flat_grads)
+        engine.grad_norm(flat_grads, max_norm, state, offs, ws, seg)
+        return state
+
+    @property
+    def clip_state(self):
+        """The io_clip_state record on the device (64 bytes, uint8; engine.read_clip_state decodes it); no
+        synchronisation.  None while clipping is off or before the first step."""
+        return self._clip_bufs[0] if self._clip_bufs is not None else None
+
+    def grad_stats(self):
+        """What the last step measured (synchronises): norm, coef, nonfinite, the cumulative steps / clipped / skipped
+        counts, and stage_norms {segment name: norm of that slice of the flat gradient buffer}."""
+        if self._clip_bufs is None:
+            raise RuntimeError("grad_stats(): no clipped step has run (max_grad_norm=%r)" % (self.max_grad_norm,))
+        state, seg, _ = self._clip_bufs
+        out = engine.read_clip_state(state)
+        sums = seg.cpu().tolist()
+        out["stage_norms"] = {name: math.sqrt(v) if v >= 0 else float("nan") for name, v in zip(self._seg_names, sums)}
+        return out
+
+
+class FusedSGD(_GradClip, torch.optim.Optimizer):
+    def __init__(self, module, lr, momentum=0.9, weight_decay=0.0, max_grad_norm=None):
+        self._clip_init(max_grad_norm)
         net = getattr(module, "module", module)     # DistModule / FixModule wrap the ResNet
         if not hasattr(net, "flat_params"):
             raise TypeError("FusedSGD needs an instaorder_amd ResNet (flat parameter buffer)")
@@ -53,7 +156,7 @@ class FusedSGD(torch.optim.Optimizer):
             raise ValueError("FusedSGD: nesterov / dampening are not supported")
         buf = self._ensure_buf()
         engine.sgd_momentum(self._net.flat_params, self._net.flat_grads, buf, g["lr"], g["momentum"],
-                            g["weight_decay"])
+                            g["weight_decay"], clip_state=self._measure(self._net.flat_grads))
         return None
 
     # ---- checkpoint interchange with torch.optim.SGD ------------------------------------------------
@@ -161,11 +264,12 @@ class _FlatLayout(torch.optim.Optimizer):
         raise KeyError("parameter is not in the flat buffer")
 
 
-class FlatSGD(_FlatLayout):
+class FlatSGD(_GradClip, _FlatLayout):
     """Momentum-SGD over the flat layout of _FlatLayout: the update is the same single HIP launch as FusedSGD.
     torch.optim.SGD semantics / state_dict layout as above."""
 
-    def __init__(self, module, lr, momentum=0.9, weight_decay=0.0):
+    def __init__(self, module, lr, momentum=0.9, weight_decay=0.0, max_grad_norm=None):
+        self._clip_init(max_grad_norm)
         defaults = dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False)
         super(FlatSGD, self).__init__(_trainable(module), defaults)
         self._buf = torch.zeros_like(self.flat_params)
@@ -175,7 +279,8 @@ class FlatSGD(_FlatLayout):
         g = self.param_groups[0]
         if not gathered:
             self.gather_grads()
-        engine.sgd_momentum(self.flat_params, self.flat_grads, self._buf, g["lr"], g["momentum"], g["weight_decay"])
+        engine.sgd_momentum(self.flat_params, self.flat_grads, self._buf, g["lr"], g["momentum"], g["weight_decay"],
+                            clip_state=self._measure(self.flat_grads))
         from . import ops
         ops.WEIGHTS_EPOCH[0] += 1          # parameters changed in place, invisibly to torch's version counters
         return None
@@ -213,7 +318,7 @@ def _adam_defaults(lr, betas, eps, weight_decay):
     return {k: v for k, v in probe.param_groups[0].items() if k != "params"}
 
 
-class _AdamFlat(object):
+class _AdamFlat(_GradClip):
     """torch.optim.Adam (amsgrad / maximize off, coupled L2) over a flat fp32 parameter buffer; mixed into a
     torch.optim.Optimizer.  The subclass provides ``_params`` (group order), ``_begin[i]`` (float offset of parameter i's
     storage, 16-byte aligned, increasing with i), ``_flat()`` -> (params, grads) and ``_state_view(buf, i)``.
@@ -291,10 +396,11 @@ class _AdamFlat(object):
         m, v = self._ensure_state()
         b1, b2 = g["betas"]
         n = len(self._params)
+        clip = self._measure(flat_g)            # one record for every launch below (None: clipping off)
         for first, last, t in self._runs(g["weight_decay"]):
             end = self._begin[last + 1] if last + 1 < n else flat_p.numel()
             engine.adam_step(flat_p, flat_g, m, v, g["lr"], b1, b2, g["eps"], g["weight_decay"], t,
-                             self._begin[first], end)
+                             self._begin[first], end, clip_state=clip)
         self._steps = [s + 1 if l else s for s, l in zip(self._steps, self._live)]
 
     # ---- checkpoint interchange with torch.optim.Adam --------------------------------------------------------------
@@ -340,7 +446,8 @@ class FusedAdam(_AdamFlat, torch.optim.Optimizer):
     """torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay) for the instaorder_amd ResNet: the update runs
     over its flat fp32 master buffers (``flat_params`` / ``flat_grads``, in fp32 and bf16 mode alike)."""
 
-    def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+    def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, max_grad_norm=None):
+        self._clip_init(max_grad_norm)
         net = getattr(module, "module", module)     # DistModule / FixModule wrap the ResNet
         if not hasattr(net, "flat_params"):
             raise TypeError("FusedAdam needs an instaorder_amd ResNet (flat parameter buffer)")
@@ -382,7 +489,8 @@ class FlatAdam(_AdamFlat, _FlatLayout):
     is what the last gather_grads / gather_stage saw (a parameter ops.WeightPlan fills counts as having one); a replayed
     hipGraph keeps what its capture saw."""
 
-    def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+    def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, max_grad_norm=None):
+        self._clip_init(max_grad_norm)
         super(FlatAdam, self).__init__(_trainable(module), _adam_defaults(lr, betas, eps, weight_decay))
         self._begin = [off for off, _ in self._spans]
         self._adam_layout()

@@ -40,18 +40,37 @@ class SingleStageModel(object):
             self.world_size = 1
         self.net = net
 
+        # `clip_grad_norm` (absent / None: off, the reference's behaviour): global-norm gradient clipping with the
+        # non-finite step guard of optim._GradClip; float('inf') only measures and guards
+        clip = params.get("clip_grad_norm")
         if params["optim"] == "SGD" and not hasattr(net, "flat_params"):
-            self.optim = FlatSGD(self.model, lr=params["lr"], momentum=0.9, weight_decay=params["weight_decay"])
+            self.optim = FlatSGD(self.model, lr=params["lr"], momentum=0.9, weight_decay=params["weight_decay"],
+                                 max_grad_norm=clip)
         elif params["optim"] == "SGD":
             self.optim = FusedSGD(self.model, lr=params["lr"], momentum=0.9,
-                                  weight_decay=params["weight_decay"])
+                                  weight_decay=params["weight_decay"], max_grad_norm=clip)
         elif params["optim"] == "Adam":
             # single_stage_model.py:39-41: torch.optim.Adam(lr, betas=(beta1, 0.999)); params['weight_decay'] is not
             # passed there either, so Adam runs without weight decay
             cls = FusedAdam if hasattr(net, "flat_params") else FlatAdam
-            self.optim = cls(self.model, lr=params["lr"], betas=(params["beta1"], 0.999))
+            self.optim = cls(self.model, lr=params["lr"], betas=(params["beta1"], 0.999), max_grad_norm=clip)
         else:
             raise Exception("No such optimizer: {}".format(params["optim"]))
+        if hasattr(net, "grad_stage_slices"):
+            self._hand_grad_segments()
+
+    RESNET_STAGE_NAMES = ("heads+layer4", "layer3", "layer2", "layer1+stem")
+
+    def _hand_grad_segments(self):
+        """With clipping on, the optimiser reports one gradient norm per backward stage (grad_stats()['stage_norms']):
+        the ResNet's grad_stage_slices(), or the wrapper's own (the MiDaS nets: _DepthBase, which calls this once its
+        stage plan can be laid out)."""
+        if getattr(self.optim, "max_grad_norm", None) is None:
+            return
+        if hasattr(self.net, "grad_stage_slices"):
+            self.optim.set_grad_segments(self.net.grad_stage_slices(), self.RESNET_STAGE_NAMES)
+        elif hasattr(self, "grad_stage_slices"):
+            self.optim.set_grad_segments(self.grad_stage_slices(), self.STAGE_NAMES)
 
     def forward_only(self, ret_loss=True):
         pass

@@ -404,6 +404,7 @@ class _DepthBase(SingleStageModel):
         self._buckets = None
         self._dp_graphs = None
         self._dp_key = None
+        self._hand_grad_segments()          # clip_grad_norm: per-stage gradient norms over grad_stage_slices()
 
     # inputs ----------------------------------------------------------------------------------------------------------
     def _keep(self, name, t):

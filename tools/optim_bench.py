@@ -6,7 +6,10 @@ step with each.  Device-event medians over warmed iterations; prints one JSON li
   (b) update of InstaDepthNet_od's 680 parameters: FlatAdam.step(gathered=True) vs torch.optim.Adam
   (c) InstaDepthNet_od training step, bf16, 384^2, 16 pairs (BASELINE configs[4]) with optim: Adam: torch.optim.Adam
       (eager per-tensor path) vs FlatAdam (flat buffer, WeightPlan, hipGraph)
-usage: python tools/optim_bench.py [--iters 100] [--warmup 10] [--step-iters 10] [--skip-step]"""
+  (d) --clip: gradient clipping on both flat buffers, momentum SGD and Adam: the fused clipped step (io_grad_norm + the
+      clipped update) vs torch.nn.utils.clip_grad_norm_ over the parameter views followed by the plain fused step vs the
+      plain fused step alone
+usage: python tools/optim_bench.py [--iters 100] [--warmup 10] [--step-iters 10] [--skip-step] [--clip]"""
 import argparse
 import json
 import os
@@ -71,6 +74,53 @@ def update_bench(args):
     return out
 
 
+def clip_bench(args):
+    """Per flat buffer and optimiser: (a) fused clipped step, (b) clip_grad_norm_ over the views + the plain fused step,
+    (c) the plain fused step.  max_grad_norm 1.0 is far below the norm of the random gradients, so (a) and (b) scale."""
+    from instaorder_amd import midas_net, resnet_cls
+    from instaorder_amd.optim import FlatAdam, FlatSGD, FusedAdam, FusedSGD
+    out = {}
+
+    def rows(opt, step, params, n, bytes_per_float):
+        def torch_then_fused():
+            torch.nn.utils.clip_grad_norm_(params, 1.0)
+            step()
+        opt.max_grad_norm = None
+        plain = timed(step, args.iters, args.warmup)
+        both = timed(torch_then_fused, args.iters, args.warmup)
+        opt.max_grad_norm = 1.0
+        fused = timed(step, args.iters, args.warmup)
+        stats = opt.grad_stats()
+        assert stats["steps"] == args.iters + args.warmup and stats["skipped"] == 0
+        return dict(floats=n, fused_clipped_ms=round(fused, 4), torch_clip_plus_fused_ms=round(both, 4),
+                    unclipped_ms=round(plain, 4), extra_ms=round(fused - plain, 4),
+                    speedup_vs_torch_clip=round(both / fused, 2),
+                    clipped_TBs=round((bytes_per_float + 4.0) * n / (fused * 1e-3) / 1e12, 2))
+
+    net = resnet_cls.resnet50_cls(in_channels=5, num_classes=[2, 3]).cuda()
+    net.flat_grads.normal_()
+    net.attach_grads()
+    params = list(net.parameters())
+    n = net.flat_params.numel()
+    for name, opt, bpf in (("sgd", FusedSGD(net, lr=1e-9, momentum=0.9, weight_decay=1e-4), 20.0),
+                           ("adam", FusedAdam(net, lr=1e-9, betas=(0.9, 0.999)), 28.0)):
+        out["resnet50_" + name] = rows(opt, opt.step, params, n, bpf)
+    del net, opt, params
+    for name, cls, kw, bpf in (("sgd", FlatSGD, dict(momentum=0.9, weight_decay=1e-4), 20.0),
+                               ("adam", FlatAdam, dict(betas=(0.9, 0.999)), 28.0)):
+        torch.manual_seed(0)
+        mod = midas_net.InstaDepthNet_od(None, non_negative=True).cuda()
+        opt = cls(mod, lr=1e-9, **kw)
+        opt.flat_grads.normal_()
+        for p, (off, k) in zip(opt._params, opt._spans):
+            p.grad = opt.flat_grads[off:off + k].view(p.shape)
+        out["instadepthnet_od_" + name] = rows(opt, lambda: opt.step(gathered=True), opt._params, opt.flat_params.numel(),
+                                               bpf)
+        del mod, opt
+        torch.cuda.empty_cache()
+    return out
+
+
 def step_bench(args):
     import instaorder_amd as ia
     from instaorder_amd import synthetic
@@ -103,9 +153,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--step-iters", type=int, default=10)
     ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--clip", action="store_true", help="only the gradient-clipping rows (d)")
     args = ap.parse_args()
     from instaorder_amd import _lib
     _lib.require_gpu()
+    if args.clip:
+        print(json.dumps(dict(bench="optim_clip", csrc=_lib.csrc_digest(), iters=args.iters, clip=clip_bench(args))))
+        return
     out = dict(bench="optim_adam", csrc=_lib.csrc_digest(), update=update_bench(args))
     if not args.skip_step:
         out["train_step"] = step_bench(args)

@@ -4,7 +4,8 @@
 (datasets.SupOcclusionOrderBatches + BatchPrefetcher) -> set_input / step -> reduce_tensors -> checkpoint ->
 validation with the 'patch' inference driver + precision / recall / F1 (tools/test.py:402-495, inference.py:794-802),
 and a resume from the checkpoint that continues the same index stream and learning-rate schedule.
-usage: python tools/train_synthetic.py [--iters 120] [--batch 64] [--size 128] [--dtype fp32|bf16] [--out DIR]"""
+usage: python tools/train_synthetic.py [--iters 120] [--batch 64] [--size 128] [--dtype fp32|bf16] [--out DIR]
+                                       [--clip-grad-norm X|inf]"""
 import argparse
 import os
 import sys
@@ -43,6 +44,9 @@ def main(argv=None):
     ap.add_argument("--resume-at", type=int, default=0, help="stop at this iteration, reload the checkpoint, continue")
     ap.add_argument("--seed", type=int, default=-1, help=">= 0: seed torch's generator first (init_weights draws from it; "
                     "at lr 0.01 the trajectory -- and how well 400 iterations learn -- depends on the draw)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, help="global-norm gradient clipping with the non-finite "
+                    "step guard (config key clip_grad_norm); 'inf' measures and guards without scaling.  The gradient "
+                    "statistics are printed with the loss")
     a = ap.parse_args(argv)
     if a.seed >= 0:
         torch.manual_seed(a.seed)
@@ -50,6 +54,8 @@ def main(argv=None):
     mcfg = dict(algo="InstaOrderNet_o", lr=0.01, weight_decay=1e-4, optim="SGD", backbone_arch="resnet50_cls",
                 backbone_param=dict(in_channels=5, num_classes=2), use_rgb=True, dtype=a.dtype,
                 lr_steps=[int(a.iters * 0.7)], lr_mults=[0.1], warmup_lr=[], warmup_steps=[])
+    if a.clip_grad_norm is not None:
+        mcfg["clip_grad_norm"] = a.clip_grad_norm
     dcfg = dict(input_size=a.size, patch_or_image="patch", data_mean=[0.485, 0.456, 0.406],
                 data_std=[0.229, 0.224, 0.225], load_rgb=True, use_category=False, dataset="InstaOrder",
                 remove_occ_bidirec=0, base_aug=dict(flip=True, shift=[-0.2, 0.2], scale=[0.8, 1.2]))
@@ -81,6 +87,11 @@ def main(argv=None):
                 print("iter %4d  lr %.4g  loss %.4f  (%.0f pairs/s)" % (curr, model.optim.param_groups[0]["lr"],
                                                                       float(loss), a.batch * (k + 1) / (time.time() - t0)),
                       flush=True)
+                if a.clip_grad_norm is not None:
+                    gs = model.optim.grad_stats()
+                    print("           grad norm %.4g  coef %.4g  clipped %d  skipped %d of %d steps  stages: %s"
+                          % (gs["norm"], gs["coef"], gs["clipped"], gs["skipped"], gs["steps"],
+                             "  ".join("%s %.3g" % kv for kv in gs["stage_norms"].items())), flush=True)
         model.save_state(out, last_iter)                                    # single_stage_model.py:66-72
         return model
 
