@@ -107,7 +107,9 @@ int io_conv2d_wgrad(const float* x, const float* dy, float* dw, int N, int H, in
                     int S, int stride, int pad, void* workspace, size_t workspace_bytes, hipStream_t stream);
 int io_filter_transpose(const float* w, int Cout, int taps, int Cin, float* wt, hipStream_t stream);
 
-/* ---- BatchNorm2d (resnet_cls.py:142, :87-92, :189), G independent statistic groups ----------- */
+/* ---- BatchNorm2d (resnet_cls.py:142, :87-92, :189), G independent statistic groups -----------
+ * Any G >= 1 with G | M.  io_bn_stats_finalize*, io_bn_bwd* and io_bn_bwd_coefs* need M > 0: an empty or negative batch is
+ * IO_ERR_SHAPE (no launch, nothing written), not a no-op. */
 size_t io_bn_partial_floats(int M, int C, int G);
 /* training statistics of y[M][C] (M = N*H*W rows, G consecutive equal groups): writes per-group
  * mean, rstd, scale = gamma*rstd, shift = beta ([G][C] each) and advances the running
@@ -137,7 +139,8 @@ int io_bn_bwd(const float* dout, const float* act, const float* mask_scale, cons
               hipStream_t stream);
 
 /* ---- pooling / heads ------------------------------------------------------------------------
- * nn.MaxPool2d(3, 2, 1) (resnet_cls.py:144); idx: one byte per output element (packed x4). */
+ * nn.MaxPool2d(3, 2, 1) (resnet_cls.py:144); idx: one byte per output element (packed x4): the first maximum of the
+ * window in (kh, kw) order, for a window of nothing but -inf its first in-bounds tap (both as PyTorch). */
 int io_maxpool_fwd(const float* x, int N, int H, int W, int C, float* out, uint32_t* idx, hipStream_t stream);
 int io_maxpool_bwd(const float* dy, const uint32_t* idx, int N, int H, int W, int C, float* dx,
                    hipStream_t stream);
@@ -313,6 +316,8 @@ int io_bn_apply_bits_dt(const void* y, int M, int C, int G, int per_group_tables
 int io_bn_apply_dt(const void* y, int M, int C, int G, int per_group_tables, const float* mean, const float* scale,
                    const float* shift, const void* identity, const float* mean2, const float* scale2,
                    const float* shift2, int relu, void* out, int dtype, hipStream_t stream);
+/* The backward forms move 16-byte chunks like io_bn_apply_dt: C must be 4 * 2^k for fp32 and 8 * 2^k for bf16 (bf16 with
+ * C = 4 is IO_ERR_SHAPE in io_bn_bwd_dt and io_bn_bwd_coefs_dt). */
 int io_bn_bwd_dt(const void* dout, const void* act, const float* mask_scale, const float* mask_shift, const void* y,
                  int M, int C, int G, const float* gamma, const float* mean, const float* rstd, float* dgamma,
                  float* dbeta, void* dy, void* dz_out, float* partial, size_t partial_floats, float* coef, int dtype,

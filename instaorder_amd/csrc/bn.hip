@@ -415,13 +415,13 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
                                                              const float* __restrict__ xmean = nullptr,
                                                              const float* __restrict__ xrstd = nullptr,
                                                              float* __restrict__ c3 = nullptr) {
-    constexpr int U = 16, MAXG = 8;
+    constexpr int U = 16;
     __shared__ double sh[2][32][8];
     const int tx = threadIdx.x & 7, ty = threadIdx.x >> 3;     // tx: channel, ty: partial lane (0..31)
     const int c = blockIdx.x * 8 + tx;
     const bool ok = c < C;
     double dg = 0.0, db = 0.0;
-    for (int g = 0; g < G && g < MAXG; ++g) {
+    for (int g = 0; g < G; ++g) {
         double a = 0.0, b2 = 0.0;
         for (int b0 = ty; b0 < nb; b0 += 32 * U) {
             float v1[U], v2[U];
@@ -673,10 +673,11 @@ __global__ __launch_bounds__(256) void bn_sum_tiles_kernel(const float* __restri
 int io_bn_bwd_from_tiles(float* p1, float* p2, const void* dz, const void* y, int M, int C, int G,
                          const float* gamma, const float* mean, const float* rstd, float* dgamma, float* dbeta,
                          void* dy, float* coef, hipStream_t st, int dt) {
-    const int sh = ilog2_exact(C / 4);
-    IO_REQUIRE(C % 4 == 0 && sh >= 0 && C <= 2048, IO_ERR_SHAPE, "bn_bwd_from_tiles: C=%d unsupported", C);
-    IO_REQUIRE(G >= 1 && M % G == 0 && (M / G) % kIoStatTileRows == 0, IO_ERR_SHAPE,
-               "bn_bwd_from_tiles: rows per group must be a multiple of %d", kIoStatTileRows);
+    const int vec = 16 / io_dtype_bytes(dt), cv = C / vec;
+    IO_REQUIRE(C % vec == 0 && ilog2_exact(cv) >= 0 && C <= 2048, IO_ERR_SHAPE,
+               "bn_bwd_from_tiles: C=%d must be %d*2^k, at most 2048", C, vec);
+    IO_REQUIRE(M > 0 && G >= 1 && M % G == 0 && (M / G) % kIoStatTileRows == 0, IO_ERR_SHAPE,
+               "bn_bwd_from_tiles: rows per group must be a positive multiple of %d", kIoStatTileRows);
     const int Mg = M / G, nt = Mg / kIoStatTileRows;
     IoProfScope prof(IO_PROF_BN_BWD, 0.0, (double)io_dtype_bytes(dt) * M * C * 3.0, st);
     const float* q1 = p1;
@@ -694,7 +695,6 @@ int io_bn_bwd_from_tiles(float* p1, float* p2, const void* dz, const void* y, in
     float* c2 = coef + (size_t)G * C;
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(io_cdiv(C, 8)), dim3(256), 0, st, q1, q2, nb, G, Mg, C, dgamma,
                        dbeta, c1, c2);
-    const int vec = 16 / io_dtype_bytes(dt), cv = C / vec;
     const size_t per_group = (size_t)Mg * cv;
     dim3 agrid(stream_blocks(per_group, cv, G), G);
     if (dt == IO_BF16)
@@ -752,7 +752,7 @@ int io_bn_stats_finalize_t(const void* y, int M, int C, int G, const float* gamm
                            float* rstd, float* scale, float* shift, float* partial, size_t partial_floats,
                            hipStream_t st, int dt) {
     IO_REQUIRE(C % 4 == 0 && C <= 2048 && ilog2_exact(C / 4) >= 0, IO_ERR_SHAPE, "bn_stats: C=%d unsupported", C);
-    IO_REQUIRE(G >= 1 && M % G == 0, IO_ERR_SHAPE, "bn_stats: M=%d not divisible by G=%d", M, G);
+    IO_REQUIRE(M > 0 && G >= 1 && M % G == 0, IO_ERR_SHAPE, "bn_stats: M=%d must be positive and divisible by G=%d", M, G);
     IO_REQUIRE(partial_floats >= io_bn_partial_floats(M, C, G), IO_ERR_WORKSPACE, "bn_stats: partial too small");
     const int Mg = M / G;
     int nb;
@@ -836,9 +836,10 @@ int io_bn_bwd_t(const void* dout, const void* act, const float* mask_scale, cons
                 hipStream_t st, int dt) {
     IO_REQUIRE(!(act && mask_scale), IO_ERR_SHAPE, "bn_bwd: give the activation OR the mask tables, not both");
     IO_REQUIRE((mask_scale == nullptr) == (mask_shift == nullptr), IO_ERR_SHAPE, "bn_bwd: mask tables come in pairs");
-    const int sh = ilog2_exact(C / 4);
-    IO_REQUIRE(C % 4 == 0 && sh >= 0 && C <= 2048, IO_ERR_SHAPE, "bn_bwd: C=%d unsupported", C);
-    IO_REQUIRE(G >= 1 && M % G == 0, IO_ERR_SHAPE, "bn_bwd: M=%d not divisible by G=%d", M, G);
+    const int vec = 16 / io_dtype_bytes(dt), cv = C / vec;
+    IO_REQUIRE(C % vec == 0 && ilog2_exact(cv) >= 0 && C <= 2048, IO_ERR_SHAPE, "bn_bwd: C=%d must be %d*2^k, at most 2048",
+               C, vec);
+    IO_REQUIRE(M > 0 && G >= 1 && M % G == 0, IO_ERR_SHAPE, "bn_bwd: M=%d must be positive and divisible by G=%d", M, G);
     IO_REQUIRE(partial_floats >= io_bn_partial_floats(M, C, G), IO_ERR_WORKSPACE, "bn_bwd: partial too small");
     const int Mg = M / G;
     int nb;
@@ -849,7 +850,6 @@ int io_bn_bwd_t(const void* dout, const void* act, const float* mask_scale, cons
     float* c2 = coef + (size_t)G * C;
     IoProfScope prof(IO_PROF_BN_BWD, 0.0,
                      (double)io_dtype_bytes(dt) * M * C * ((act ? 6.0 : 4.0) + 1.0 + (dz_out ? 1.0 : 0.0)), st);
-    const int vec = 16 / io_dtype_bytes(dt), cv = C / vec;
     const size_t per_group = (size_t)Mg * cv;
     dim3 agrid(stream_blocks(per_group, cv, G), G);
 #define IO_BN_BWD(T_)                                                                                               \
@@ -881,9 +881,10 @@ extern "C" int io_bn_bwd(const float* dout, const float* act, const float* mask_
 int io_bn_bwd_coefs_t(const void* dz, const void* y, int M, int C, int G, const float* gamma, const float* mean,
                       const float* rstd, float* dgamma, float* dbeta, float* coef, float* partial,
                       size_t partial_floats, hipStream_t st, int dt, const float* mask_scale, const float* mask_shift) {
-    const int sh = ilog2_exact(C / 4);
-    IO_REQUIRE(C % 4 == 0 && sh >= 0 && C <= 2048, IO_ERR_SHAPE, "bn_bwd_coefs: C=%d unsupported", C);
-    IO_REQUIRE(G >= 1 && M % G == 0, IO_ERR_SHAPE, "bn_bwd_coefs: M=%d not divisible by G=%d", M, G);
+    const int vec = 16 / io_dtype_bytes(dt);
+    IO_REQUIRE(C % vec == 0 && ilog2_exact(C / vec) >= 0 && C <= 2048, IO_ERR_SHAPE,
+               "bn_bwd_coefs: C=%d must be %d*2^k, at most 2048", C, vec);
+    IO_REQUIRE(M > 0 && G >= 1 && M % G == 0, IO_ERR_SHAPE, "bn_bwd_coefs: M=%d must be positive and divisible by G=%d", M, G);
     IO_REQUIRE((mask_scale == nullptr) == (mask_shift == nullptr), IO_ERR_SHAPE, "bn_bwd_coefs: the mask tables come in pairs");
     IO_REQUIRE(partial_floats >= io_bn_partial_floats(M, C, G), IO_ERR_WORKSPACE, "bn_bwd_coefs: partial too small");
     const int Mg = M / G;

@@ -78,7 +78,9 @@ __global__ __launch_bounds__(kThreads) void maxpool_fwd_kernel(const T* __restri
             sh = *reinterpret_cast<const f32x4*>(xh + (size_t)gi * C + q * 4);
         }
         f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        uint32_t bi[4] = {0, 0, 0, 0};
+        // the tap a window of nothing but -inf keeps: its first in-bounds one (as PyTorch), not tap 0 in the padding
+        const uint32_t t0 = (ho == 0 ? 3 : 0) + (wo == 0 ? 1 : 0);
+        uint32_t bi[4] = {t0, t0, t0, t0};
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh) {
             const int h = ho * 2 - 1 + kh;
@@ -184,9 +186,11 @@ __global__ __launch_bounds__(kThreads) void maxpool_fwd_rows_kernel(const T* __r
         const int q = j - wo * CV;
         f32x4 mu[NV], sc[NV], sh[NV], best[NV];
         uint32_t bi[NV];
+        // the tap a window of nothing but -inf keeps: its first in-bounds one (as PyTorch), not tap 0 in the padding
+        const uint32_t t0 = ((ho == 0 ? 3u : 0u) + (wo == 0 ? 1u : 0u)) * 0x01010101u;
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
-            mu[k] = 0.f; sc[k] = 1.f; sh[k] = 0.f; best[k] = -INFINITY; bi[k] = 0;
+            mu[k] = 0.f; sc[k] = 1.f; sh[k] = 0.f; best[k] = -INFINITY; bi[k] = t0;
             if constexpr (XF) {
                 const size_t to = (size_t)gi * C + q * VEC + 4 * k;
                 if (xm) mu[k] = *reinterpret_cast<const f32x4*>(xm + to);

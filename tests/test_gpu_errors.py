@@ -64,6 +64,35 @@ def test_bn_pool_loss_sgd_reject_bad_arguments():
     bad(L().io_pack_planes_nhwc8(planes, strides, 6, 1, 8, 8, P(b), ST()))
 
 
+def test_bn_launchers_reject_an_empty_batch_and_bf16_half_chunks():
+    """M = 0 (once an integer division by zero on the host), M < 0 (once a launch with a negative row count) and bf16 with
+    C = 4 (zero 8-channel chunks per row: once a division by zero on the device and table reads far out of bounds) are
+    error codes with a message; nothing is written."""
+    nan = lambda n, dtype=torch.float32: torch.full((n,), float("nan"), device=DEV, dtype=dtype)    # noqa: E731
+    a, b = buf(), buf()
+    gam, mu, rs = torch.ones(64, device=DEV), torch.zeros(64, device=DEV), torch.ones(64, device=DEV)
+    outs = [nan(64) for _ in range(6)] + [nan(1 << 12), nan(1 << 12), nan(256), nan(1 << 12)]
+    tab = outs[:4]
+    dg, db, dy, dz, coef, part = outs[4:]
+    for M in (0, -64):
+        bad(L().io_bn_stats_finalize(P(a), M, 64, 1, P(gam), P(mu), None, None, 0.1, 1e-5, P(tab[0]), P(tab[1]), P(tab[2]),
+                                     P(tab[3]), P(part), 1 << 12, ST()))
+        bad(L().io_bn_bwd(P(a), None, None, None, P(b), M, 64, 1, P(gam), P(mu), P(rs), P(dg), P(db), P(dy), P(dz), P(part),
+                          1 << 12, P(coef), ST()))
+        bad(L().io_bn_bwd_coefs_dt(P(a), P(b), M, 64, 1, P(gam), P(mu), P(rs), P(dg), P(db), P(coef), P(part), 1 << 12, 0, ST()))
+    ah, bh = a.bfloat16(), b.bfloat16()
+    dyh, dzh = nan(1 << 12, torch.bfloat16), nan(1 << 12, torch.bfloat16)
+    bad(L().io_bn_bwd_dt(P(ah), None, None, None, P(bh), 64, 4, 1, P(gam), P(mu), P(rs), P(dg), P(db), P(dyh), P(dzh), P(part),
+                         1 << 12, P(coef), 1, ST()))
+    bad(L().io_bn_bwd_coefs_dt(P(ah), P(bh), 64, 4, 1, P(gam), P(mu), P(rs), P(dg), P(db), P(coef), P(part), 1 << 12, 1, ST()))
+    torch.cuda.synchronize()
+    for t in outs + [dyh, dzh]:
+        assert bool(torch.isnan(t).all())
+    # fp32 with C = 4 stays supported (one 4-channel chunk per row)
+    assert L().io_bn_bwd_coefs_dt(P(a), P(b), 64, 4, 1, P(gam), P(mu), P(rs), P(dg), P(db), P(coef), P(part), 1 << 12, 0, ST()) == 0
+    torch.cuda.synchronize()
+
+
 def test_network_executor_rejects_bad_calls():
     heads = (C.c_int * 1)(2)
     assert not L().io_net_create(9, 1, heads)                                               # in_channels > 5

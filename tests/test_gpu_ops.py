@@ -730,6 +730,8 @@ def test_avgpool_fc(heads):
 
 
 def _ref_losses(z, B, Kocc, Kdep, occ_t, dep_t, ov, w_ov, w_di, inv_world):
+    """ov [B] or None.  A row whose ov is neither 0 nor 1 belongs to neither subset (supervised_order.py:62-73): it adds
+    nothing to the depth loss and its label is never looked at (it may lie outside the head)."""
     z = z.clone().requires_grad_(True)
     l_occ = torch.zeros((), dtype=torch.float64)
     l_dep = torch.zeros((), dtype=torch.float64)
