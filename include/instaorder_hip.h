@@ -634,6 +634,28 @@ int io_pair_planes_u8_hw(const uint8_t* arena, size_t arena_bytes, const io_pair
                          const io_pair_desc* desc_host, int P, int SH, int SW, const double* mean3, const double* std3,
                          float* rgb, float* modal1, float* modal2, hipStream_t stream);
 
+/* ---- run-length-encoded instance masks (COCO RLE) decoded on the device, in front of io_pair_planes_u8_hw / io_mask_pack.
+ * A mask of H x W is a list of run lengths over its pixels in COLUMN-major order (q = x * H + y), alternating 0, 1, 0, ...
+ * and starting with a run of zeros; zero-length runs may appear anywhere.  The caller ships, per mask, the inclusive prefix
+ * sums `ends` of the run lengths: pixel q lies in run r = #{k : ends[k] <= q}, and out[y * W + x] = (r & 1) ? value : 0.
+ * One launch decodes n masks, which may differ in size, into row-major uint8 images at byte offsets of `out` (any
+ * alignment; full 4-byte words are stored as words).  desc_dev / desc_host are the same n descriptors in device and host
+ * memory; the host copy is validated (H, W > 0, H * W < 2^31, n_runs >= 1, value in 0..255, table inside ends_count
+ * entries, output inside out_bytes, n <= 65535; IO_ERR_SHAPE otherwise, nothing launched).  The kernel is safe whatever
+ * the table CONTENTS are: the search reads entries [0, n_runs) only and its result selects one of two byte values.
+ * Tables of at most IO_RLE_LDS_RUNS entries are searched in LDS, longer ones in global memory.  No workspace. */
+#define IO_RLE_LDS_RUNS 4096
+typedef struct io_rle_desc {
+    int64_t ends_off;   /* first entry of this mask's inclusive prefix sums, in uint32 units */
+    int32_t n_runs;
+    int32_t H, W;
+    int32_t value;      /* byte written where the run index is odd: 1, or a category id */
+    int64_t out_off;    /* byte offset of the row-major H*W output */
+} io_rle_desc;
+int io_rle_decode_u8(const uint32_t* ends_dev, size_t ends_count, const io_rle_desc* desc_dev,
+                     const io_rle_desc* desc_host, int n, uint8_t* out, size_t out_bytes, hipStream_t stream);
+int io_rle_lds_runs(void);   /* IO_RLE_LDS_RUNS of the built library */
+
 /* ---- measurement aid (bench.py): HIP-event timing of every launch, per kernel class, on the launch
  * stream.  Process-global; io_prof_end synchronises on the recorded events and returns the number of
  * classes written.  flops / bytes are the ALGORITHMIC figures of the timed launches (the direct convolution's count). */

@@ -41,6 +41,12 @@ class PairDesc(C.Structure):
                 ("flip", C.c_int32), ("interp", C.c_int32)]
 
 
+class RleDesc(C.Structure):
+    """io_rle_desc of include/instaorder_hip.h"""
+    _fields_ = [("ends_off", C.c_int64), ("n_runs", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("value", C.c_int32), ("out_off", C.c_int64)]
+
+
 class DgradFused(C.Structure):
     """io_dgrad_fused of include/instaorder_hip.h (device pointers as integers, None = NULL)"""
     _fields_ = [(n, C.c_void_p) for n in ("xb_y", "xb_coef", "xb_dy_out", "add", "relu_mask", "ep_y", "ep_mean", "ep_rstd",
@@ -97,6 +103,9 @@ SIGNATURES = {
     "io_pack_planes_nhwc8": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_long), _I, _I, _I, _I, _P, _P]),
     "io_pair_planes_u8": (_I, [_P, _Z, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "io_pair_planes_u8_hw": (_I, [_P, _Z, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    # ends_dev, ends_count, desc_dev, desc_host, n, out, out_bytes, stream
+    "io_rle_decode_u8": (_I, [_P, _Z, _P, _P, _I, _P, _Z, _P]),
+    "io_rle_lds_runs": (_I, []),
     "io_order_loss": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _F, _F, _F, _P, _P, _P]),
     "io_sgd_momentum": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P]),
     # params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, stream

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rle import RLEMasks
 
 INTER_LINEAR, INTER_CUBIC, INTER_CUBIC_F64 = 1, 2, 3     # io_pair_desc.interp
 
@@ -85,6 +86,7 @@ class PairRenderer(object):
         self._pinned = [None, None]
         self._events = [None, None]
         self._turn = 0
+        self.last_upload = None      # bytes the last render() sent to the device: images / masks (or run tables) / descriptors
 
     def _staging(self, nbytes):
         """two pinned staging buffers used alternately; a buffer is reused only after its upload has completed"""
@@ -96,63 +98,151 @@ class PairRenderer(object):
             self._pinned[k] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
         return k, self._pinned[k]
 
+    @staticmethod
+    def _check_item(images, masks, ii, load_rgb):
+        n, H, W = masks[ii].shape
+        if not isinstance(masks[ii], RLEMasks) and masks[ii].dtype != np.uint8:
+            raise TypeError("instance masks must be uint8 (got %s)" % masks[ii].dtype)
+        if load_rgb and (images[ii].shape != (H, W, 3) or images[ii].dtype != np.uint8):
+            raise ValueError("image %d: expected uint8 [%d,%d,3], got %s %s" % (ii, H, W, images[ii].dtype,
+                                                                               images[ii].shape))
+        return n, H, W
+
+    @staticmethod
+    def _fill_desc(d, image_off, mask1_off, mask2_off, H, W, box, interp, flip):
+        d.image_off, d.mask1_off, d.mask2_off = image_off, mask1_off, mask2_off
+        d.H, d.W = H, W
+        d.x, d.y, d.w, d.h = [int(v) for v in box]
+        d.flip = int(bool(flip))
+        d.interp = int(interp)
+
+    @staticmethod
+    def _fill_stage(host, images, masks, placed):
+        """placed: (key, offset) of every image ("img", ii) and dense mask ("m", ii, i) that is uploaded"""
+        for key, o in placed:
+            src = images[key[1]] if key[0] == "img" else masks[key[1]][key[2]]
+            host[o:o + src.size] = np.ascontiguousarray(src).reshape(-1)
+
+    def _upload_done(self, slot, stream):
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._events[slot] = ev
+
+    def _launch(self, arena, nbytes, desc_dev, desc, load_rgb, stream):
+        P, S, SH = len(desc), self.S, self.SH
+        rgb = torch.empty((P, 3, SH, S), device=self.device) if load_rgb else None
+        m1 = torch.empty((P, 1, SH, S), device=self.device)
+        m2 = torch.empty((P, 1, SH, S), device=self.device)
+        rc = _lib.lib().io_pair_planes_u8_hw(
+            C.c_void_p(arena), C.c_size_t(nbytes), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p), P, SH, S,
+            C.cast(self.mean, C.c_void_p), C.cast(self.std, C.c_void_p),
+            C.c_void_p(rgb.data_ptr()) if load_rgb else None, C.c_void_p(m1.data_ptr()), C.c_void_p(m2.data_ptr()),
+            C.c_void_p(stream.cuda_stream))
+        _lib.check(rc, "io_pair_planes_u8_hw")
+        if rgb is None:
+            rgb = torch.zeros((P, 3, SH, S), device=self.device)     # occ_order_dataset.py:231-232
+        return rgb, m1, m2
+
     def render(self, images, masks, items, load_rgb=True):
         """images: list of uint8 [H,W,3] arrays (entries may be None when load_rgb is False); masks: list of uint8
-        [n,H,W] arrays, one per image; items: list of (image_index, idx1, idx2, (x, y, w, h), interp, flip)."""
+        [n,H,W] arrays or ``rle.RLEMasks``, one per image; items: list of (image_index, idx1, idx2, (x, y, w, h), interp,
+        flip)."""
         P = len(items)
         if P == 0:
             raise ValueError("PairRenderer.render: empty batch")
-        S, SH = self.S, self.SH
+        if any(isinstance(m, RLEMasks) for m in masks):
+            return self._render_rle(images, masks, items, load_rgb)
         # arena layout: every referenced image once, every referenced mask once (16-byte aligned)
         off, cursor = {}, 0
+        sent = {"img": 0, "m": 0}
 
         def place(key, nbytes):
             nonlocal cursor
             if key not in off:
                 off[key] = cursor
                 cursor = (cursor + nbytes + 15) // 16 * 16
+                sent[key[0]] += nbytes
             return off[key]
 
         desc = (_lib.PairDesc * P)()
         for k, (ii, i1, i2, box, interp, flip) in enumerate(items):
-            n, H, W = masks[ii].shape
-            if masks[ii].dtype != np.uint8:
-                raise TypeError("instance masks must be uint8 (got %s)" % masks[ii].dtype)
-            d = desc[k]
-            d.image_off = place(("img", ii), H * W * 3) if load_rgb else 0
-            d.mask1_off = place(("m", ii, int(i1)), H * W)
-            d.mask2_off = place(("m", ii, int(i2)), H * W)
-            d.H, d.W = H, W
-            d.x, d.y, d.w, d.h = [int(v) for v in box]
-            d.flip = int(bool(flip))
-            d.interp = int(interp)
-            if load_rgb and (images[ii].shape != (H, W, 3) or images[ii].dtype != np.uint8):
-                raise ValueError("image %d: expected uint8 [%d,%d,3], got %s %s" % (ii, H, W, images[ii].dtype,
-                                                                                   images[ii].shape))
+            n, H, W = self._check_item(images, masks, ii, load_rgb)
+            image_off = place(("img", ii), H * W * 3) if load_rgb else 0
+            self._fill_desc(desc[k], image_off, place(("m", ii, int(i1)), H * W), place(("m", ii, int(i2)), H * W),
+                            H, W, box, interp, flip)
         nbytes = max(cursor, 16)
         dbytes = C.sizeof(desc)
         slot, stage = self._staging(nbytes + dbytes)
         host = stage.numpy()
-        for key, o in off.items():
-            src = images[key[1]] if key[0] == "img" else masks[key[1]][key[2]]
-            host[o:o + src.size] = np.ascontiguousarray(src).reshape(-1)
+        self._fill_stage(host, images, masks, off.items())
         host[nbytes:nbytes + dbytes] = np.frombuffer(desc, dtype=np.uint8)
         dev = stage[:nbytes + dbytes].to(self.device, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self._events[slot] = ev
-        rgb = torch.empty((P, 3, SH, S), device=self.device) if load_rgb else None
-        m1 = torch.empty((P, 1, SH, S), device=self.device)
-        m2 = torch.empty((P, 1, SH, S), device=self.device)
-        rc = _lib.lib().io_pair_planes_u8_hw(
-            C.c_void_p(dev.data_ptr()), C.c_size_t(nbytes), C.c_void_p(dev.data_ptr() + nbytes),
-            C.cast(desc, C.c_void_p), P, SH, S, C.cast(self.mean, C.c_void_p), C.cast(self.std, C.c_void_p),
-            C.c_void_p(rgb.data_ptr()) if load_rgb else None, C.c_void_p(m1.data_ptr()), C.c_void_p(m2.data_ptr()),
-            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _lib.check(rc, "io_pair_planes_u8_hw")
-        if rgb is None:
-            rgb = torch.zeros((P, 3, SH, S), device=self.device)     # occ_order_dataset.py:231-232
-        return rgb, m1, m2
+        stream = torch.cuda.current_stream(self.device)
+        self._upload_done(slot, stream)
+        self.last_upload = dict(images=sent["img"], masks=sent["m"], descriptors=dbytes, total=nbytes + dbytes)
+        return self._launch(dev.data_ptr(), nbytes, dev.data_ptr() + nbytes, desc, load_rgb, stream)
+
+    def _render_rle(self, images, masks, items, load_rgb):
+        """render() for a batch in which at least one image carries ``rle.RLEMasks``.  The arena lives on the device and
+        only part of it is uploaded: one device buffer [images and dense masks | run tables | decode descriptors | pair
+        descriptors | decoded masks], of which everything before the decoded masks comes through the pinned staging
+        buffer in one copy.  One ``io_rle_decode_u8`` launch fills the slot of every referenced run-length mask, then
+        ``io_pair_planes_u8_hw`` runs on the arena as it does for dense masks."""
+        from . import rle
+        P = len(items)
+        up, dec = {}, {}                     # key -> offset inside its region
+        cursors = {id(up): 0, id(dec): 0}
+        sent = {"img": 0, "m": 0}
+
+        def place(region, key, nbytes):
+            if key not in region:
+                region[key] = cursors[id(region)]
+                cursors[id(region)] = (cursors[id(region)] + nbytes + 15) // 16 * 16
+                if region is up:
+                    sent[key[0]] += nbytes
+            return key
+
+        keys = []
+        for ii, i1, i2, box, interp, flip in items:
+            n, H, W = self._check_item(images, masks, ii, load_rgb)
+            region = dec if isinstance(masks[ii], RLEMasks) else up
+            keys.append((place(up, ("img", ii), H * W * 3) if load_rgb else None, region,
+                         place(region, ("m", ii, range(n)[int(i1)]), H * W),
+                         place(region, ("m", ii, range(n)[int(i2)]), H * W)))
+        dec_keys = list(dec)
+        ends, rdesc = rle.descriptors([(masks[k[1]], k[2]) for k in dec_keys], [0] * len(dec_keys))
+        desc = (_lib.PairDesc * P)()
+        tab_at = max(cursors[id(up)], 16)
+        rd_at = tab_at + (ends.nbytes + 15) // 16 * 16
+        pd_at = rd_at + (C.sizeof(rdesc) + 15) // 16 * 16
+        dec_at = pd_at + (C.sizeof(desc) + 15) // 16 * 16             # = the bytes that are uploaded
+        nbytes = dec_at + max(cursors[id(dec)], 16)
+        for k, key in enumerate(dec_keys):
+            rdesc[k].out_off = dec_at + dec[key]
+        for k, ((ii, i1, i2, box, interp, flip), (kimg, region, k1, k2)) in enumerate(zip(items, keys)):
+            base = dec_at if region is dec else 0
+            _, H, W = masks[ii].shape
+            self._fill_desc(desc[k], up[kimg] if load_rgb else 0, base + region[k1], base + region[k2], H, W, box, interp,
+                            flip)
+        slot, stage = self._staging(dec_at)
+        host = stage.numpy()
+        self._fill_stage(host, images, masks, up.items())
+        host[tab_at:tab_at + ends.nbytes] = ends.view(np.uint8)
+        host[rd_at:rd_at + C.sizeof(rdesc)] = np.frombuffer(rdesc, dtype=np.uint8)
+        host[pd_at:pd_at + C.sizeof(desc)] = np.frombuffer(desc, dtype=np.uint8)
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        dev[:dec_at].copy_(stage[:dec_at], non_blocking=True)
+        stream = torch.cuda.current_stream(self.device)
+        self._upload_done(slot, stream)
+        self.last_upload = dict(images=sent["img"], masks=sent["m"] + ends.nbytes,
+                                descriptors=C.sizeof(rdesc) + C.sizeof(desc), total=dec_at)
+        base = dev.data_ptr()
+        if dec_keys:
+            rc = _lib.lib().io_rle_decode_u8(C.c_void_p(base + tab_at), C.c_size_t(ends.size), C.c_void_p(base + rd_at),
+                                             C.cast(rdesc, C.c_void_p), len(dec_keys), C.c_void_p(base),
+                                             C.c_size_t(nbytes), C.c_void_p(stream.cuda_stream))
+            _lib.check(rc, "io_rle_decode_u8")
+        return self._launch(base, nbytes, base + pd_at, desc, load_rgb, stream)
 
 
 # ---- item logic of the datasets ----------------------------------------------------------------------------------------
@@ -179,6 +269,12 @@ class _Batches(object):
 
     def _instances(self, idx):
         modal, category, bboxes, amodal, image_fn = self.data_reader.get_image_instances(idx, with_gt=True)
+        if isinstance(modal, RLEMasks):                           # run-length masks stay encoded up to the device
+            if self.config.get("use_category", False):
+                if len(modal) and np.max(category) > 255:
+                    raise ValueError("use_category with category ids above 255 does not fit the uint8 mask arena")
+                modal = modal.with_values(category)
+            return modal, bboxes, image_fn
         if self.config.get("use_category", False):
             modal = modal * category[:, None, None]               # occ_order_dataset.py:184-185
             if modal.max() > 255:
@@ -215,7 +311,8 @@ class SupOcclusionOrderBatches(_Batches):
         if self.config["dataset"] == "KINS":
             from . import inference as infer
             amodal = self.data_reader.get_image_instances(idx, with_gt=True)[3]
-            gt = infer.infer_gt_order(modal, amodal)
+            host = modal.to_dense() if isinstance(modal, RLEMasks) else modal
+            gt = infer.infer_gt_order(host, amodal.to_dense() if isinstance(amodal, RLEMasks) else amodal)
         elif self.config["dataset"] == "InstaOrder":
             gt = self.data_reader.get_gt_ordering(idx, type="occlusion", rm_bidirec=self.config["remove_occ_bidirec"])
         else:
@@ -282,7 +379,8 @@ class SupDepthOccOrderBatches(_Batches):
     def _get_pair_ind(self, img_id):
         """depth_occ_order_dataset.py:150-160 (no category scaling, no re-draw in this class)."""
         modal, category, bboxes, amodal, image_fn = self.data_reader.get_image_instances(img_id, with_gt=True)
-        modal = np.ascontiguousarray(modal.astype(np.uint8))
+        if not isinstance(modal, RLEMasks):
+            modal = np.ascontiguousarray(modal.astype(np.uint8))
         gt_depth = self.data_reader.get_gt_ordering(img_id, type="depth", rm_overlap=self.config["remove_depth_overlap"])
         gt_occ = self.data_reader.get_gt_ordering(img_id, type="occlusion", rm_bidirec=self.config["remove_occ_bidirec"])
         return modal, bboxes, image_fn, gt_depth, gt_occ

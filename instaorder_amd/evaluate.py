@@ -79,7 +79,12 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
     for q in range(beg, end):
         i = q % n
         modal, category, bboxes, amodal_gt, image_fn = data_reader.get_image_instances(i, with_gt=True)
-        if kind != "SupDepthOccOrderDataset" and data_cfg.get("use_category", False):
+        if infer._is_rle(modal):            # run-length masks (rle.RLEReader): pixels only where a host rule needs them
+            if kind != "SupDepthOccOrderDataset" and data_cfg.get("use_category", False):
+                modal = modal.with_values(category)
+            if rules is infer or callable(order_method):
+                modal = modal.to_dense()
+        elif kind != "SupDepthOccOrderDataset" and data_cfg.get("use_category", False):
             modal = modal * category[:, None, None]
         image = None if (callable(order_method) or order_method in ("area", "yaxis")) else np.asarray(load_image(image_fn))
         boxes = expand_bbox(bboxes, data_cfg["enlarge_box"])
@@ -101,7 +106,7 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
                                                                      mode, size, disp_select_method, mask_rules=mask_rules)
             else:
                 rgb, masks = infer.resize_mode_inputs(next(model.model.parameters()).device, image, modal, size) \
-                    if mode == "resize" else _identity_inputs(image, modal, size)
+                    if mode == "resize" else _identity_inputs(image, infer._host_masks(modal, None), size)
                 res = infer.infer_depthnet_batched(model, rgb, masks, pairs=rules.select_pairs(modal, pairs))
                 pred_occ, pred_dep = res["occ_order"], res["depth_order"]
         elif want_dep:

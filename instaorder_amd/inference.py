@@ -297,6 +297,17 @@ def infer_order_batched(model, rgb, masks, method, pairs=None, max_pairs=256, re
 _RENDERERS = {}
 
 
+def _is_rle(masks):
+    from .rle import RLEMasks
+    return isinstance(masks, RLEMasks)
+
+
+def _host_masks(masks, mr):
+    """Run-length masks (``rle.RLEMasks``) stay encoded for the device rules and the renderer; the host rules
+    (``mask_rules='host'``: mr is None) work on pixels, so they are decoded once here."""
+    return masks.to_dense() if mr is None and _is_rle(masks) else masks
+
+
 def _preprocess_pairs(model, image, inmodal, bboxes, pair_list, patch_or_image, input_size):
     """The per-pair pre-processing of inference.py:449-482 on the device (datasets.PairRenderer): 'patch' = square
     crop around the pair (zero padded), INTER_CUBIC; 'image' = zero padding to a square, INTER_LINEAR; masks
@@ -307,7 +318,7 @@ def _preprocess_pairs(model, image, inmodal, bboxes, pair_list, patch_or_image, 
     if patch_or_image not in ("patch", "image"):
         raise ValueError("patch_or_image=%r: one of 'patch', 'image', 'resize', 'orig'" % (patch_or_image,))
     dev = model.net.flat_params.device
-    modal = np.ascontiguousarray(inmodal.astype(np.uint8))
+    modal = inmodal if _is_rle(inmodal) else np.ascontiguousarray(inmodal.astype(np.uint8))
     image = np.ascontiguousarray(image.astype(np.uint8))
     _, hh, ww = modal.shape
     items = []
@@ -344,7 +355,7 @@ def resize_mode_inputs(dev, image, inmodal, input_size):
 
 def _whole_image_inputs(dev, image, inmodal, size):
     from . import datasets
-    modal = np.ascontiguousarray(inmodal.astype(np.uint8))
+    modal = inmodal if _is_rle(inmodal) else np.ascontiguousarray(inmodal.astype(np.uint8))
     image = np.ascontiguousarray(image.astype(np.uint8))
     n, hh, ww = modal.shape
     box = (0, 0, ww, hh)
@@ -386,6 +397,7 @@ def _select_pairs(mr, inmodal, pairs):
 
 def _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size, mask_rules="host"):
     mr = _mask_rules(mask_rules)
+    inmodal = _host_masks(inmodal, mr)
     pair_list = _select_pairs(mr, inmodal, pairs)
     n = inmodal.shape[0]
     if not pair_list:
@@ -397,8 +409,9 @@ def _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, inp
                       else orig_mode_inputs(dev, image, inmodal))
         return infer_order_batched(model, rgb, masks, method, pairs=pair_list)
     planes = _preprocess_pairs(model, image, inmodal, bboxes, pair_list, patch_or_image, input_size)
-    return infer_order_batched(model, None, torch.from_numpy(np.asarray(inmodal)), method, pairs=pair_list,
-                               pair_planes=planes)
+    # with pair planes the driver takes only the instance count from ``masks``
+    count = torch.empty((n, 0)) if _is_rle(inmodal) else torch.from_numpy(np.asarray(inmodal))
+    return infer_order_batched(model, None, count, method, pairs=pair_list, pair_planes=planes)
 
 
 def infer_order_sup_occ(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size=256, use_rgb=True,
@@ -504,6 +517,7 @@ def infer_order_sup_depth(model, image, inmodal, bboxes, pairs, method, patch_or
     ``mask_rules='device'``: pair selection and the per-pair disparity statistics run on the device
     (``mask_rules.select_pairs`` / ``depth_orders_from_disp``); the masks of the 'resize' / 'orig' modes stay there."""
     mr = _mask_rules(mask_rules)
+    inmodal = _host_masks(inmodal, mr)
     if method == "InstaOrderNet_d":
         return _infer_sup(model, image, inmodal, bboxes, pairs, method, patch_or_image, input_size,
                           mask_rules)["depth_order"], None
@@ -516,7 +530,7 @@ def infer_order_sup_depth(model, image, inmodal, bboxes, pairs, method, patch_or
             rgb, masks = orig_mode_inputs(dev, image, inmodal)
         elif patch_or_image == "image" and image.shape[0] == image.shape[1] == input_size:
             from .synthetic import image_mode_inputs
-            rgb, masks = image_mode_inputs(image, inmodal, input_size)
+            rgb, masks = image_mode_inputs(image, _host_masks(inmodal, None), input_size)
             rgb, masks = torch.from_numpy(rgb).to(dev), torch.from_numpy(masks)
         else:
             raise NotImplementedError("midas_pretrained: patch_or_image='resize' / 'orig', or 'image' on square images of "
@@ -554,7 +568,7 @@ def infer_order_sup_depth(model, image, inmodal, bboxes, pairs, method, patch_or
             rgb, masks = rgb.cpu().numpy(), masks.cpu().numpy()
     elif patch_or_image == "image" and image.shape[0] == image.shape[1] == input_size:
         from .synthetic import image_mode_inputs
-        rgb, masks = image_mode_inputs(image, inmodal, input_size)
+        rgb, masks = image_mode_inputs(image, _host_masks(inmodal, None), input_size)
     else:
         raise NotImplementedError("InstaDepthNet inference: patch_or_image='resize' / 'orig', or 'image' on square images "
                                   "of the network size (per-pair crops would run the MiDaS encoder once per pair)")
