@@ -549,8 +549,8 @@ int io_conv2d_fwd_resid(const float* y3, const float* identity, const float* w, 
  *   two == 0:  relu((y3 - tb[g][c]) * ta[g][c] + tc[g][c] + second)   ta / tb / tc = scale / mean / shift of bn3, second = identity
  *   two != 0:  relu(ta[g][c] * y3 + tb[g][c] * second + tc[g][c])     a block with a downsample branch: second = the downsample
  *              convolution's raw output, the two BatchNorms folded into one table set (io_bn_resid2_tables)
- * written to `out` (optional) and, as [out > 0] one bit per element (word (m * Cin + c) / 32, bit c % 32; optional, bf16
- * 256-row kernel only), to out_bits.  tile_mean / tile_m2 (a pair, optional): per-(128-row tile, channel) mean / M2 of y,
+ * written to `out` (optional) and, as [out > 0] one bit per element (word (m * Cin + c) / 32, bit c % 32; optional, needs
+ * `out`), to out_bits -- by the bf16 256-row kernel next to `out`, on every other route by a follow-up launch that packs `out`.  tile_mean / tile_m2 (a pair, optional): per-(128-row tile, channel) mean / M2 of y,
  * io_bn_tile_partial_floats(M, Cout, G) floats each, for io_bn_finalize_tiles.  bf16: launches of whole 256-row tiles with
  * 64 | Cin, 128 | Cout and 256 | rows per group run on conv_p256_kernel, the transform applied IN LDS to each A k-tile
  * after its DMA has landed (IO_P256_XOP=0 / io_set_bf16_p256_xop(0): on conv_nt_kernel's staging registers instead). */

@@ -2805,6 +2805,25 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
+// [t > 0] as one bit per element in the layout of IoBwStats::xb_bits / maskbits (word i = elements 32 i .. 32 i + 31, bit
+// = element % 32): one thread per word.  What the 256-row bf16 kernel writes next to xb_out; conv_nt_kernel has no such
+// side output, so its launcher packs the tensor it wrote.
+template <typename T>
+__global__ __launch_bounds__(256) void pack_sign_bits_kernel(const T* __restrict__ t, uint32_t* __restrict__ bits,
+                                                             size_t nwords) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nwords) return;
+    const T* p = t + i * 32;
+    uint32_t w = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const f32x4 v = io_ldv(p + 4 * q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w |= (v[e] > 0.f ? 1u : 0u) << (4 * q + e);
+    }
+    bits[i] = w;
+}
+
 // floats per output channel of the filter (gradient) a launch addresses
 inline size_t io_filter_row(const IoConvGeom& g) {
     return g.cr ? (size_t)io_stem_kp(g.wT, g.cr) : (size_t)g.wT * (g.gw ? g.gw : g.Ci);
@@ -2979,6 +2998,10 @@ int io_launch_conv_nt(const IoConvGeom& g, const void* in, const void* wgt, void
         }
     }
     g_last_route.store(0, std::memory_order_relaxed);
+    // the one-bit mask of the residual forms' side output: conv_nt_kernel does not write it, a follow-up launch packs it from
+    // the tensor (below) -- so a caller that passed xb_bits finds them written on every route
+    IO_REQUIRE(!bws.xb_bits || (bws.xb_res && bws.xb_out), IO_ERR_SHAPE,
+               "conv_nt: xb_bits is the mask of the residual forms' side output (needs xb_res and xb_out)");
     // Output-channel tile: 128 wide where that leaves enough tiles to fill the chip, 64 wide otherwise -- a small per-GPU batch
     // (the reference's own 32 pairs per GPU, or a strong-scaling rank) gives layers 3-4 only 32..128 row tiles, and 128-wide
     // tiles then occupy a fraction of the 256 CUs with one block each (measured at 32 pairs: 43-51 TF/s on the 8 x 8 maps).
@@ -3148,7 +3171,17 @@ int io_launch_conv_nt(const IoConvGeom& g, const void* in, const void* wgt, void
 #undef IO_LAUNCH_NT
 #undef IO_LAUNCH_NT__
 #undef IO_LAUNCH_NT_
-    return io_check_launch("conv_nt");
+    int rc = io_check_launch("conv_nt");
+    if (rc || !bws.xb_bits) return rc;
+    // (LIN: xb_out is the dense [M][Ci] operand tensor, 32 | Ci)
+    const size_t nwords = (size_t)M * g.Ci / 32;
+    IO_REQUIRE(nwords / 256 + 1 < (1UL << 31), IO_ERR_SHAPE, "conv_nt: mask bits grid too large");
+    const dim3 pgrid((unsigned)((nwords + 255) / 256));
+    if (dt_in == IO_BF16)
+        hipLaunchKernelGGL(pack_sign_bits_kernel<bf16_t>, pgrid, dim3(256), 0, st, (const bf16_t*)bws.xb_out, bws.xb_bits, nwords);
+    else
+        hipLaunchKernelGGL(pack_sign_bits_kernel<float>, pgrid, dim3(256), 0, st, (const float*)bws.xb_out, bws.xb_bits, nwords);
+    return io_check_launch("conv_nt(mask bits)");
 }
 
 int io_launch_conv_wgrad(const IoConvGeom& g, const void* in, const void* dy, float* dw, float* partial,

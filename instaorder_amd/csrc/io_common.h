@@ -169,8 +169,9 @@ struct IoBwStats {
     // xb_res == 2: the block has a downsample branch -- operand = relu(xb_a * y3 + xb_b * yd + xb_c) with xb_y = yd (the
     // downsample convolution's output) and the two BatchNorms folded into one table set (io_bn_resid2_tables).
     int xb_res;
-    // xb_res != 0 on the 256-row bf16 kernel (conv_p256.hip): [operand > 0] of the tensor written to xb_out as one bit per
-    // element (the layout of maskbits below), for the data gradient that later masks by this block output.  Optional.
+    // xb_res != 0: [operand > 0] of the tensor written to xb_out as one bit per element (the layout of maskbits below), for
+    // the data gradient that later masks by this block output.  Optional; needs xb_out.  The 256-row bf16 kernel
+    // (conv_p256.hip) writes it next to xb_out; behind conv_nt_kernel the launcher packs it from xb_out in a second launch.
     uint32_t* xb_bits;
     // Independent again: scratch for the Winograd form of 3x3 stride-1 same-size launches (fp32, Wo even, whole 128-row
     // tiles, no add / mask): 18 * Co * Ci floats that the launcher fills with the transformed filters ([filter row][4 | 6][Co][Ci],
