@@ -656,6 +656,49 @@ int io_rle_decode_u8(const uint32_t* ends_dev, size_t ends_count, const io_rle_d
                      const io_rle_desc* desc_host, int n, uint8_t* out, size_t out_bytes, hipStream_t stream);
 int io_rle_lds_runs(void);   /* IO_RLE_LDS_RUNS of the built library */
 
+/* ---- COCO polygon instance masks rasterised on the device (csrc/poly.hip, DESIGN.md "Polygon masks"), next to
+ * io_rle_decode_u8 in front of io_pair_planes_u8_hw / io_mask_pack.  The fill rule is the published COCO mask API's
+ * (frPoly + merge as a union): vertices scaled by 5 and rounded (done by the CALLER: `verts` holds the int32 pairs
+ * X = trunc(5 x + 0.5), Y = trunc(5 y + 0.5)), every edge of the closed ring walked in unit steps along its longer axis,
+ * a crossing wherever two consecutive walk points differ in X and the larger X sits on a pixel centre (X = 5 x + 3) of a
+ * column 0 <= x < W, at row y = clamp(ceil((Ymin - 2) / 5), 0, H); pixel q = x * H + y of a part is set iff the number of
+ * crossings at positions <= q is odd; an instance is the OR of its parts.
+ *   One launch sequence fills n_masks instances, which may differ in size, into row-major uint8 images at byte offsets of
+ * `out` (any alignment; stores of at most 4 bytes): out[out_off + y * W + x] = value where the instance is set, else 0;
+ * no byte outside [out_off, out_off + H * W) is touched.  Mask m owns the parts [first_part, first_part + n_parts), each of
+ * which names m; n_parts = 0 is an empty mask.  parts_* / masks_* are the same tables in device and host memory; the
+ * host copies are validated before anything is launched (H, W > 0, H * W < 2^31, value in 0..255, n_masks <= 65535, every
+ * part's vertices inside n_verts, every part owned by exactly the mask it names, outputs inside out_bytes, workspace
+ * 16-byte aligned; IO_ERR_SHAPE otherwise, IO_ERR_WORKSPACE for a workspace below io_poly_fill_workspace_bytes()).  The kernels are safe whatever
+ * the vertex VALUES are: coordinates are clamped to +-IO_POLY_MAX_COORD on load, every toggle address is checked against
+ * its plane and every store address comes from the validated descriptors.  The walk of an edge is a loop of one wave, so
+ * there is no index over all walk steps and no bound on their total.
+ *   Workspace: one offset per part, then one bit plane of H * W bits per part (column-major), zeroed on the stream by the
+ * call.  The parity scan covers IO_POLY_SCAN_WORDS 32-bit words of a plane per pass of its block. */
+#define IO_POLY_SCAN_WORDS 256
+#define IO_POLY_MAX_COORD (1 << 24)
+typedef struct io_poly_part {
+    int64_t vert_off;   /* first vertex of this part, in (x, y) pairs */
+    int32_t n_verts;    /* >= 1 */
+    int32_t mask;       /* the instance this part belongs to */
+} io_poly_part;
+typedef struct io_poly_mask {
+    int32_t H, W;
+    int32_t value;      /* byte written where the instance is set: 1, or a category id */
+    int32_t first_part;
+    int32_t n_parts;    /* 0: an empty mask */
+    int32_t reserved;
+    int64_t out_off;    /* byte offset of the row-major H*W output */
+} io_poly_mask;
+int io_poly_fill_u8(const int32_t* verts_dev, size_t n_verts, const io_poly_part* parts_dev,
+                    const io_poly_part* parts_host, int n_parts, const io_poly_mask* masks_dev,
+                    const io_poly_mask* masks_host, int n_masks, uint8_t* out, size_t out_bytes, void* workspace,
+                    size_t workspace_bytes, hipStream_t stream);
+/* 0 = tables the call would refuse (io_last_error_string says why); never 0 for valid tables */
+size_t io_poly_fill_workspace_bytes(const io_poly_part* parts_host, int n_parts, const io_poly_mask* masks_host,
+                                    int n_masks);
+int io_poly_scan_words(void);   /* IO_POLY_SCAN_WORDS of the built library */
+
 /* ---- measurement aid (bench.py): HIP-event timing of every launch, per kernel class, on the launch
  * stream.  Process-global; io_prof_end synchronises on the recorded events and returns the number of
  * classes written.  flops / bytes are the ALGORITHMIC figures of the timed launches (the direct convolution's count). */

@@ -9,6 +9,7 @@ Public surface mirrors the reference's ``models`` / ``utils`` packages for this 
     from instaorder_amd import evaluate            # tools/test.py Tester loops (P / R / F1, WHDR) over the batched drivers
     from instaorder_amd import datasets            # SupOcclusionOrderBatches, SupDepthOccOrderBatches, SupDepthOrderBatches, PairRenderer
     from instaorder_amd import rle                 # RLEMasks, RLEReader, decode: run-length (COCO RLE) masks decoded on the device
+    from instaorder_amd import poly                # PolyMasks, decode: COCO polygon masks rasterised on the device
 
 Importing the package does not load the HIP library; the first op does, and fails loudly when
 it is missing or no gfx950 device is visible (there is no CPU fallback).
@@ -32,9 +33,9 @@ def __getattr__(name):
         ns = _types.SimpleNamespace(resnet50_cls=resnet_cls.resnet50_cls, ResNet=resnet_cls.ResNet,
                                     FixModule=common_utils.FixModule)
         return ns
-    if name == "rle":
+    if name in ("rle", "poly"):
         import importlib
-        return importlib.import_module(".rle", __name__)
+        return importlib.import_module("." + name, __name__)
     if name == "utils":
         from . import common_utils, distributed_utils, scheduler
         ns = _types.SimpleNamespace()

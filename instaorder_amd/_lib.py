@@ -47,6 +47,17 @@ class RleDesc(C.Structure):
                 ("value", C.c_int32), ("out_off", C.c_int64)]
 
 
+class PolyPart(C.Structure):
+    """io_poly_part of include/instaorder_hip.h"""
+    _fields_ = [("vert_off", C.c_int64), ("n_verts", C.c_int32), ("mask", C.c_int32)]
+
+
+class PolyMask(C.Structure):
+    """io_poly_mask of include/instaorder_hip.h"""
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("value", C.c_int32), ("first_part", C.c_int32),
+                ("n_parts", C.c_int32), ("reserved", C.c_int32), ("out_off", C.c_int64)]
+
+
 class DgradFused(C.Structure):
     """io_dgrad_fused of include/instaorder_hip.h (device pointers as integers, None = NULL)"""
     _fields_ = [(n, C.c_void_p) for n in ("xb_y", "xb_coef", "xb_dy_out", "add", "relu_mask", "ep_y", "ep_mean", "ep_rstd",
@@ -106,6 +117,11 @@ SIGNATURES = {
     # ends_dev, ends_count, desc_dev, desc_host, n, out, out_bytes, stream
     "io_rle_decode_u8": (_I, [_P, _Z, _P, _P, _I, _P, _Z, _P]),
     "io_rle_lds_runs": (_I, []),
+    # verts_dev, n_verts, parts_dev, parts_host, n_parts, masks_dev, masks_host, n_masks, out, out_bytes, workspace,
+    # workspace_bytes, stream
+    "io_poly_fill_u8": (_I, [_P, _Z, _P, _P, _I, _P, _P, _I, _P, _Z, _P, _Z, _P]),
+    "io_poly_fill_workspace_bytes": (_Z, [_P, _I, _P, _I]),
+    "io_poly_scan_words": (_I, []),
     "io_order_loss": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _F, _F, _F, _P, _P, _P]),
     "io_sgd_momentum": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P]),
     # params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, stream

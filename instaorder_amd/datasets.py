@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .rle import RLEMasks
+from .rle import is_encoded
 
 INTER_LINEAR, INTER_CUBIC, INTER_CUBIC_F64 = 1, 2, 3     # io_pair_desc.interp
 
@@ -86,7 +86,7 @@ class PairRenderer(object):
         self._pinned = [None, None]
         self._events = [None, None]
         self._turn = 0
-        self.last_upload = None      # bytes the last render() sent to the device: images / masks (or run tables) / descriptors
+        self.last_upload = None      # bytes the last render() sent to the device: images / masks (or run tables, vertices) / descriptors
 
     def _staging(self, nbytes):
         """two pinned staging buffers used alternately; a buffer is reused only after its upload has completed"""
@@ -101,7 +101,7 @@ class PairRenderer(object):
     @staticmethod
     def _check_item(images, masks, ii, load_rgb):
         n, H, W = masks[ii].shape
-        if not isinstance(masks[ii], RLEMasks) and masks[ii].dtype != np.uint8:
+        if not is_encoded(masks[ii]) and masks[ii].dtype != np.uint8:
             raise TypeError("instance masks must be uint8 (got %s)" % masks[ii].dtype)
         if load_rgb and (images[ii].shape != (H, W, 3) or images[ii].dtype != np.uint8):
             raise ValueError("image %d: expected uint8 [%d,%d,3], got %s %s" % (ii, H, W, images[ii].dtype,
@@ -145,12 +145,12 @@ class PairRenderer(object):
 
     def render(self, images, masks, items, load_rgb=True):
         """images: list of uint8 [H,W,3] arrays (entries may be None when load_rgb is False); masks: list of uint8
-        [n,H,W] arrays or ``rle.RLEMasks``, one per image; items: list of (image_index, idx1, idx2, (x, y, w, h), interp,
-        flip)."""
+        [n,H,W] arrays, ``rle.RLEMasks`` or ``poly.PolyMasks``, one per image; items: list of (image_index, idx1, idx2,
+        (x, y, w, h), interp, flip)."""
         P = len(items)
         if P == 0:
             raise ValueError("PairRenderer.render: empty batch")
-        if any(isinstance(m, RLEMasks) for m in masks):
+        if any(is_encoded(m) for m in masks):
             return self._render_rle(images, masks, items, load_rgb)
         # arena layout: every referenced image once, every referenced mask once (16-byte aligned)
         off, cursor = {}, 0
@@ -183,12 +183,14 @@ class PairRenderer(object):
         return self._launch(dev.data_ptr(), nbytes, dev.data_ptr() + nbytes, desc, load_rgb, stream)
 
     def _render_rle(self, images, masks, items, load_rgb):
-        """render() for a batch in which at least one image carries ``rle.RLEMasks``.  The arena lives on the device and
-        only part of it is uploaded: one device buffer [images and dense masks | run tables | decode descriptors | pair
-        descriptors | decoded masks], of which everything before the decoded masks comes through the pinned staging
-        buffer in one copy.  One ``io_rle_decode_u8`` launch fills the slot of every referenced run-length mask, then
-        ``io_pair_planes_u8_hw`` runs on the arena as it does for dense masks."""
-        from . import rle
+        """render() for a batch in which at least one image carries ``rle.RLEMasks`` or ``poly.PolyMasks``.  The arena
+        lives on the device and only part of it is uploaded: one device buffer [images and dense masks | run tables |
+        decode descriptors | vertices | part and mask descriptors | pair descriptors | decoded masks | polygon workspace],
+        of which everything before the decoded masks comes through the pinned staging buffer in one copy.  One
+        ``io_rle_decode_u8`` launch fills the slot of every referenced run-length mask and one ``io_poly_fill_u8`` call the
+        slot of every referenced polygon instance, then ``io_pair_planes_u8_hw`` runs on the arena as it does for dense
+        masks.  (A batch without polygons has empty polygon regions: the layout of the run-length path as it was.)"""
+        from . import poly, rle
         P = len(items)
         up, dec = {}, {}                     # key -> offset inside its region
         cursors = {id(up): 0, id(dec): 0}
@@ -205,20 +207,33 @@ class PairRenderer(object):
         keys = []
         for ii, i1, i2, box, interp, flip in items:
             n, H, W = self._check_item(images, masks, ii, load_rgb)
-            region = dec if isinstance(masks[ii], RLEMasks) else up
+            region = dec if is_encoded(masks[ii]) else up
             keys.append((place(up, ("img", ii), H * W * 3) if load_rgb else None, region,
                          place(region, ("m", ii, range(n)[int(i1)]), H * W),
                          place(region, ("m", ii, range(n)[int(i2)]), H * W)))
-        dec_keys = list(dec)
-        ends, rdesc = rle.descriptors([(masks[k[1]], k[2]) for k in dec_keys], [0] * len(dec_keys))
+        # an instance of the decoded region is a run-length code (of RLEMasks, or one inside PolyMasks) or a polygon
+        refs = [(key, (masks[key[1]], key[2]) if isinstance(masks[key[1]], rle.RLEMasks) else masks[key[1]].rle_ref(key[2]))
+                for key in dec]
+        dec_keys = [key for key, ref in refs if ref is not None]
+        pol_keys = [key for key, ref in refs if ref is None]
+        ends, rdesc = rle.descriptors([ref for key, ref in refs if ref is not None], [0] * len(dec_keys))
+        verts, pparts, pmasks, n_parts = poly.descriptors([(masks[k[1]], k[2]) for k in pol_keys], [0] * len(pol_keys))
+        pbytes = (C.sizeof(pparts), C.sizeof(pmasks)) if pol_keys else (0, 0)
         desc = (_lib.PairDesc * P)()
         tab_at = max(cursors[id(up)], 16)
         rd_at = tab_at + (ends.nbytes + 15) // 16 * 16
-        pd_at = rd_at + (C.sizeof(rdesc) + 15) // 16 * 16
+        vt_at = rd_at + (C.sizeof(rdesc) + 15) // 16 * 16
+        pp_at = vt_at + (verts.nbytes + 15) // 16 * 16
+        pm_at = pp_at + (pbytes[0] + 15) // 16 * 16
+        pd_at = pm_at + (pbytes[1] + 15) // 16 * 16
         dec_at = pd_at + (C.sizeof(desc) + 15) // 16 * 16             # = the bytes that are uploaded
         nbytes = dec_at + max(cursors[id(dec)], 16)
+        ws_at = (nbytes + 15) // 16 * 16
+        ws_bytes = poly.workspace_bytes(pparts, n_parts, pmasks) if pol_keys else 0
         for k, key in enumerate(dec_keys):
             rdesc[k].out_off = dec_at + dec[key]
+        for k, key in enumerate(pol_keys):
+            pmasks[k].out_off = dec_at + dec[key]
         for k, ((ii, i1, i2, box, interp, flip), (kimg, region, k1, k2)) in enumerate(zip(items, keys)):
             base = dec_at if region is dec else 0
             _, H, W = masks[ii].shape
@@ -229,19 +244,29 @@ class PairRenderer(object):
         self._fill_stage(host, images, masks, up.items())
         host[tab_at:tab_at + ends.nbytes] = ends.view(np.uint8)
         host[rd_at:rd_at + C.sizeof(rdesc)] = np.frombuffer(rdesc, dtype=np.uint8)
+        if pol_keys:
+            host[vt_at:vt_at + verts.nbytes] = verts.view(np.uint8).reshape(-1)
+            host[pp_at:pp_at + pbytes[0]] = np.frombuffer(pparts, dtype=np.uint8)
+            host[pm_at:pm_at + pbytes[1]] = np.frombuffer(pmasks, dtype=np.uint8)
         host[pd_at:pd_at + C.sizeof(desc)] = np.frombuffer(desc, dtype=np.uint8)
-        dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        dev = torch.empty(ws_at + ws_bytes if pol_keys else nbytes, dtype=torch.uint8, device=self.device)
         dev[:dec_at].copy_(stage[:dec_at], non_blocking=True)
         stream = torch.cuda.current_stream(self.device)
         self._upload_done(slot, stream)
-        self.last_upload = dict(images=sent["img"], masks=sent["m"] + ends.nbytes,
-                                descriptors=C.sizeof(rdesc) + C.sizeof(desc), total=dec_at)
+        self.last_upload = dict(images=sent["img"], masks=sent["m"] + ends.nbytes + verts.nbytes,
+                                descriptors=C.sizeof(rdesc) + sum(pbytes) + C.sizeof(desc), total=dec_at)
         base = dev.data_ptr()
         if dec_keys:
             rc = _lib.lib().io_rle_decode_u8(C.c_void_p(base + tab_at), C.c_size_t(ends.size), C.c_void_p(base + rd_at),
                                              C.cast(rdesc, C.c_void_p), len(dec_keys), C.c_void_p(base),
                                              C.c_size_t(nbytes), C.c_void_p(stream.cuda_stream))
             _lib.check(rc, "io_rle_decode_u8")
+        if pol_keys:
+            rc = _lib.lib().io_poly_fill_u8(C.c_void_p(base + vt_at), C.c_size_t(verts.shape[0]), C.c_void_p(base + pp_at),
+                                            C.cast(pparts, C.c_void_p), n_parts, C.c_void_p(base + pm_at),
+                                            C.cast(pmasks, C.c_void_p), len(pol_keys), C.c_void_p(base), C.c_size_t(nbytes),
+                                            C.c_void_p(base + ws_at), C.c_size_t(ws_bytes), C.c_void_p(stream.cuda_stream))
+            _lib.check(rc, "io_poly_fill_u8")
         return self._launch(base, nbytes, base + pd_at, desc, load_rgb, stream)
 
 
@@ -269,7 +294,7 @@ class _Batches(object):
 
     def _instances(self, idx):
         modal, category, bboxes, amodal, image_fn = self.data_reader.get_image_instances(idx, with_gt=True)
-        if isinstance(modal, RLEMasks):                           # run-length masks stay encoded up to the device
+        if is_encoded(modal):                                     # run-length / polygon masks stay encoded up to the device
             if self.config.get("use_category", False):
                 if len(modal) and np.max(category) > 255:
                     raise ValueError("use_category with category ids above 255 does not fit the uint8 mask arena")
@@ -311,8 +336,8 @@ class SupOcclusionOrderBatches(_Batches):
         if self.config["dataset"] == "KINS":
             from . import inference as infer
             amodal = self.data_reader.get_image_instances(idx, with_gt=True)[3]
-            host = modal.to_dense() if isinstance(modal, RLEMasks) else modal
-            gt = infer.infer_gt_order(host, amodal.to_dense() if isinstance(amodal, RLEMasks) else amodal)
+            host = modal.to_dense() if is_encoded(modal) else modal
+            gt = infer.infer_gt_order(host, amodal.to_dense() if is_encoded(amodal) else amodal)
         elif self.config["dataset"] == "InstaOrder":
             gt = self.data_reader.get_gt_ordering(idx, type="occlusion", rm_bidirec=self.config["remove_occ_bidirec"])
         else:
@@ -379,7 +404,7 @@ class SupDepthOccOrderBatches(_Batches):
     def _get_pair_ind(self, img_id):
         """depth_occ_order_dataset.py:150-160 (no category scaling, no re-draw in this class)."""
         modal, category, bboxes, amodal, image_fn = self.data_reader.get_image_instances(img_id, with_gt=True)
-        if not isinstance(modal, RLEMasks):
+        if not is_encoded(modal):
             modal = np.ascontiguousarray(modal.astype(np.uint8))
         gt_depth = self.data_reader.get_gt_ordering(img_id, type="depth", rm_overlap=self.config["remove_depth_overlap"])
         gt_occ = self.data_reader.get_gt_ordering(img_id, type="occlusion", rm_bidirec=self.config["remove_occ_bidirec"])

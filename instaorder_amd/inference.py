@@ -298,12 +298,13 @@ _RENDERERS = {}
 
 
 def _is_rle(masks):
-    from .rle import RLEMasks
-    return isinstance(masks, RLEMasks)
+    """masks that stay encoded up to the device: ``rle.RLEMasks`` or ``poly.PolyMasks``"""
+    from .rle import is_encoded
+    return is_encoded(masks)
 
 
 def _host_masks(masks, mr):
-    """Run-length masks (``rle.RLEMasks``) stay encoded for the device rules and the renderer; the host rules
+    """Run-length and polygon masks (``rle.RLEMasks``, ``poly.PolyMasks``) stay encoded for the device rules and the renderer; the host rules
     (``mask_rules='host'``: mr is None) work on pixels, so they are decoded once here."""
     return masks.to_dense() if mr is None and _is_rle(masks) else masks
 

@@ -11,7 +11,8 @@ composition is vectorised NumPy.  Every function returns exactly what its ``infe
 the definition.
 
 Masks: NumPy arrays or device tensors [n, H, W] of bool, an integer type or a float type, with integer values in
-0..255 (binary masks, or masks carrying category ids), or ``rle.RLEMasks`` (run-length codes, decoded on the device).
+0..255 (binary masks, or masks carrying category ids), or ``rle.RLEMasks`` / ``poly.PolyMasks`` (run-length codes and
+polygons, decoded on the device).
 Anything else raises ValueError before any launch.
 """
 import ctypes as C
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, inference
-from .rle import RLEMasks, decode as _rle_decode
+from .rle import is_encoded
 
 MODES = ("host", "device")
 _NONZERO, _EQ1 = 0, 1            # IO_MASK_NONZERO, IO_MASK_EQ1
@@ -39,8 +40,8 @@ _INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
 
 def _check_masks(m, name="masks"):
     """Shape / dtype / value checks: host side for NumPy input, one reduction for a device tensor.  n = 0 is allowed (the
-    host functions accept it); an empty image is not.  ``rle.RLEMasks`` were checked when they were built."""
-    if isinstance(m, RLEMasks):
+    host functions accept it); an empty image is not.  Encoded masks (``rle.RLEMasks``, ``poly.PolyMasks``) were checked when they were built."""
+    if is_encoded(m):
         return
     if torch.is_tensor(m):
         if m.dim() != 3:
@@ -82,10 +83,10 @@ def _device(like=None):
 
 
 def _to_u8(m, dev):
-    """Validated masks -> contiguous uint8 [n, H, W] on ``dev`` (no copy when they already are); run-length masks are
-    decoded there (io_rle_decode_u8)."""
-    if isinstance(m, RLEMasks):
-        return _rle_decode(m, dev)
+    """Validated masks -> contiguous uint8 [n, H, W] on ``dev`` (no copy when they already are); run-length and
+    polygon masks are decoded there (io_rle_decode_u8, io_poly_fill_u8)."""
+    if is_encoded(m):
+        return m.to_device(dev)
     if torch.is_tensor(m):
         t = m if m.dtype == torch.uint8 else m.to(torch.uint8)
         return t.to(dev).contiguous()

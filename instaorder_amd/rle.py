@@ -1,9 +1,11 @@
 """Run-length-encoded instance masks (COCO RLE) for the device input pipeline.
 
-Every dataset the reference reads stores its masks as COCO run-length codes; they are decoded to dense [n, H, W] arrays on
-the host only because a cv2 pipeline needs pixels.  Here the codes travel to the GPU as they are -- a few hundred uint32
-per mask instead of H * W bytes -- and ``io_rle_decode_u8`` (csrc/rle.hip) decodes them there, in front of the render
-kernel (``datasets.PairRenderer``) and of the mask rules (``mask_rules``).
+Of the reference's datasets KINS, and the crowd regions of COCO (InstaOrder, COCOA), store their masks as COCO run-length
+codes; every other COCO instance is a list of polygons (``poly.PolyMasks`` carries those, and codes mixed in with them).
+The reference decodes both to dense [n, H, W] arrays on the host only because a cv2 pipeline needs pixels.  Here the
+codes travel to the GPU as they are -- a few hundred uint32 per mask instead of H * W bytes -- and ``io_rle_decode_u8``
+(csrc/rle.hip) decodes them there, in front of the render kernel (``datasets.PairRenderer``) and of the mask rules
+(``mask_rules``).
 
 The format: a mask of H x W is a list of non-negative run lengths over its pixels in COLUMN-major order (q = x * H + y).
 Runs alternate 0, 1, 0, ... and start with a run of zeros, so a mask whose first pixel is set starts with the count 0;
@@ -46,7 +48,17 @@ def _counts_from_string(s):
     return counts
 
 
-class RLEMasks(object):
+class EncodedMasks(object):
+    """What the consumers test for: the n instance masks of one image in a form that stays encoded up to the device
+    (``RLEMasks``, ``poly.PolyMasks``).  A subclass offers ``shape``, ``__len__``, ``__getitem__``, ``values``,
+    ``with_values``, ``to_dense()`` (host) and ``to_device(device, out=None)`` (uint8 [n, H, W] device tensor)."""
+
+
+def is_encoded(masks):
+    return isinstance(masks, EncodedMasks)
+
+
+class RLEMasks(EncodedMasks):
     """The n instance masks of one image as run-length codes: ``counts`` is a list of n sequences of run lengths, ``values``
     the byte each mask carries where it is set (1, or a category id).  Stands in for a uint8 [n, H, W] array wherever the
     renderer, the dataset classes, ``mask_rules`` and the inference drivers take one."""
@@ -159,6 +171,9 @@ class RLEMasks(object):
             r = np.searchsorted(ends[offsets[i]:offsets[i + 1]], q, side="right")
             out[i] = ((r & 1) * int(self.values[i])).astype(np.uint8).reshape(H, W)
         return out
+
+    def to_device(self, device, out=None):
+        return decode(self, device, out=out)
 
     # ---- constructors -----------------------------------------------------------------------------------------------
     @classmethod
