@@ -699,6 +699,60 @@ size_t io_poly_fill_workspace_bytes(const io_poly_part* parts_host, int n_parts,
                                     int n_masks);
 int io_poly_scan_words(void);   /* IO_POLY_SCAN_WORDS of the built library */
 
+/* ---- baseline JPEG images decoded on the device (csrc/jpeg.hip, DESIGN.md "JPEG images"), in front of
+ * io_pair_planes_u8_hw.  The caller parses the file headers; what travels is the entropy-coded segment of every image (the
+ * bytes after the SOS header up to, not including, EOI -- FF 00 stuffing and RSTn markers still in place) in one byte pool,
+ * the distinct table sets, and one descriptor per image.  One call decodes n images, which may differ in size and
+ * sampling, into interleaved uint8 H x W x 3 images at byte offsets of `out` (any alignment; stores of at most 4 bytes; no
+ * byte outside [out_off, out_off + 3 H W) is touched).  The result is the published baseline algorithm with libjpeg's
+ * default choices (integer "islow" IDCT, triangle "fancy" chroma upsampling, 16-bit fixed-point YCbCr -> RGB), all in 32-bit
+ * integer arithmetic.
+ *   Three stages, one launch each behind a table and an offset launch: (1) entropy decode, one lane per image, to int16
+ * coefficients; (2) dequantise + IDCT, one thread per 8 x 8 block, to the component planes padded to whole MCUs; (3)
+ * upsample + colour, one thread per aligned 4-byte word of the output.  status_dev[i] (int32, written by the call's
+ * kernels) is 0 for a decoded image and one of 1 = bits that are no Huffman code, 2 = zero run past coefficient 63, 3 =
+ * RSTn missing or out of order, 4 = data exhausted, 5 = DC category above 15 for a stream that did not decode; such an
+ * image is still written (from the coefficients decoded up to the fault, zero after it) and no other image is affected.
+ *   desc_dev / desc_host and tables_dev / tables_host are the same tables in device and host memory; the host copies are
+ * validated before anything is enqueued: 1 <= H, W <= 65535 and 3 H W < 2^31, n_comp 1 (hs = vs = 1) or 3 (hs x vs = 1x1,
+ * 2x1 or 2x2), restart_interval >= 0, table_set inside tables_bytes, quant index < 4, Huffman index < 2, the code-length
+ * counts of every referenced set a prefix code of at most 256 symbols, data range inside pool_bytes, output inside
+ * out_bytes, n <= 65535, fewer than 2^31 blocks in all, workspace 16-byte aligned (IO_ERR_SHAPE otherwise; IO_ERR_WORKSPACE
+ * for a workspace below io_jpeg_workspace_bytes()).  The kernels are safe whatever the pool and table BYTES are: the entropy loop runs at most
+ * 64 passes per block, reads pool bytes of its own range only and stores inside its own coefficient range.
+ *   Workspace: one block offset per image, the derived Huffman tables per set, 128 bytes of coefficients (zeroed on the
+ * stream by the call) and 64 bytes of planes per 8 x 8 block. */
+#define IO_JPEG_LDS_TABLE_SETS 8   /* a batch with at most this many table sets decodes with its Huffman tables in LDS */
+typedef struct io_jpeg_tables {
+    uint16_t quant[4][64];         /* quantisation tables 0..3 in the zig-zag order of the DQT segment */
+    uint8_t huff_counts[4][16];    /* [0], [1]: DC tables 0, 1; [2], [3]: AC tables 0, 1; codes of length 1..16 (DHT) */
+    uint8_t huff_symbols[4][256];  /* symbols in code order; all-zero counts: table absent */
+} io_jpeg_tables;
+typedef struct io_jpeg_desc {
+    int64_t data_off;          /* first byte of the entropy-coded segment in the pool */
+    int64_t out_off;           /* byte offset of the interleaved H x W x 3 output */
+    int32_t data_bytes;
+    int32_t H, W;
+    int32_t n_comp;            /* 1: grayscale (R = G = B = Y); 3: YCbCr, chroma sampled 1 x 1 */
+    int32_t hs, vs;            /* luma sampling: 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0) */
+    int32_t restart_interval;  /* MCUs between RSTn markers, 0: none */
+    int32_t table_set;         /* index into the io_jpeg_tables array */
+    uint8_t quant[4];          /* per component: quantisation table, DC and AC Huffman table ([3] unused) */
+    uint8_t dc[4];
+    uint8_t ac[4];
+    int32_t reserved;
+} io_jpeg_desc;
+int io_jpeg_decode_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev,
+                      const io_jpeg_tables* tables_host, size_t tables_bytes, const io_jpeg_desc* desc_dev,
+                      const io_jpeg_desc* desc_host, int n, uint8_t* out, size_t out_bytes, void* workspace,
+                      size_t workspace_bytes, int32_t* status_dev, hipStream_t stream);
+/* 0 = descriptors the call would refuse (io_last_error_string says why); never 0 for valid ones */
+size_t io_jpeg_workspace_bytes(const io_jpeg_desc* desc_host, int n);
+/* images one wave64 of the entropy stage decodes side by side, one lane each (1..64, default 1; a tuning knob, process-global) */
+int io_jpeg_set_images_per_wave(int images);
+int io_jpeg_get_images_per_wave(void);
+int io_jpeg_lds_table_sets(void);   /* IO_JPEG_LDS_TABLE_SETS of the built library */
+
 /* ---- measurement aid (bench.py): HIP-event timing of every launch, per kernel class, on the launch
  * stream.  Process-global; io_prof_end synchronises on the recorded events and returns the number of
  * classes written.  flops / bytes are the ALGORITHMIC figures of the timed launches (the direct convolution's count). */

@@ -1,0 +1,454 @@
+// Baseline JPEG files -> interleaved uint8 RGB images, on the device (DESIGN.md "JPEG images").
+//
+// The headers are parsed by the caller; per image the entropy-coded bytes, a table set and a descriptor arrive
+// (include/instaorder_hip.h).  The result is the published baseline algorithm with libjpeg's default choices, integer only:
+//   0. jpeg_offsets_kernel   exclusive prefix sum of the images' 8 x 8 block counts: where an image's coefficients (128 B
+//      jpeg_tables_kernel    per block) and planes (64 B per block) start; the derived Huffman tables of every table set.
+//   1. jpeg_entropy_kernel   the sequential part (jpeg_entropy.h): ONE LANE PER IMAGE, io_jpeg_set_images_per_wave() lanes (default 1)
+//                            of a wave64 in use; the bytes are read eight at a time, the derived tables from LDS when the
+//                            batch has at most IO_JPEG_LDS_TABLE_SETS sets, else from global memory.  Writes the non-zero quantised
+//                            coefficients as int16 into the zeroed coefficient range and a status word per image.
+//   2. jpeg_idct_kernel      one thread per block: dequantise, the "islow" IDCT of jidctint.c (13-bit constants, columns
+//                            descaled by 11, rows by 18, + 128, clamp), 8 x 8 bytes into the component plane, which is
+//                            padded to whole MCUs.
+//   3. jpeg_colour_kernel    as rle_decode_kernel: a thread owns one aligned 4-byte word of the output, computes the (at
+//                            most two) pixels its bytes belong to -- triangle upsampling of the chroma planes over their
+//                            REAL width and height, 16-bit fixed-point YCbCr -> RGB -- and stores the word once.
+// All arithmetic is 32-bit two's complement, which holds every intermediate of a stream an encoder made from 8-bit samples.
+//
+// Safety does not depend on the pool or table bytes: see jpeg_entropy.h for stage 1; stages 2 and 3 read and write only
+// addresses that follow from the descriptors the host validated, and every sample is clamped to a byte before it is stored.
+#include "io_common.h"
+#include "jpeg_entropy.h"
+
+#include <atomic>
+
+namespace {
+
+constexpr int kThreads = 256;                // four wave64
+constexpr int kWordsPerThread = 4;           // colour: 16 output bytes per thread and chunk
+constexpr int kChunkWords = kThreads * kWordsPerThread;
+static_assert(sizeof(io_jpeg_tables) == 1600 && sizeof(io_jpeg_desc) == 64, "ABI layout of the JPEG tables");
+static_assert(sizeof(JpegHuff) == 904, "four derived tables per set keep 16-byte alignment");
+
+// images per wave64 of the entropy stage.  Measured on 256 noise images of 640 x 480 (tools/jpeg_input_bench.py): 1 was the
+// fastest of 64 / 16 / 4 / 1 -- the lanes of a wave diverge on every symbol and each waits for the others' memory reads
+std::atomic<int> g_images_per_wave{1};
+
+struct Geo {
+    int mw, mh;          // MCUs across and down
+    int bpm;             // blocks per MCU
+    long n_blocks;
+    int ystride, cstride;// bytes per row of the padded luma / chroma plane
+    long ybytes, cbytes; // bytes of the padded luma plane / of one chroma plane
+};
+
+__host__ __device__ inline Geo geometry(const io_jpeg_desc& d) {
+    Geo g;
+    g.mw = (d.W + 8 * d.hs - 1) / (8 * d.hs);
+    g.mh = (d.H + 8 * d.vs - 1) / (8 * d.vs);
+    g.bpm = d.hs * d.vs + (d.n_comp == 3 ? 2 : 0);
+    g.n_blocks = (long)g.mw * g.mh * g.bpm;
+    g.ystride = g.mw * 8 * d.hs;
+    g.cstride = g.mw * 8;
+    g.ybytes = (long)g.ystride * (g.mh * 8 * d.vs);
+    g.cbytes = d.n_comp == 3 ? (long)g.cstride * (g.mh * 8) : 0;
+    return g;
+}
+
+// off[i] = blocks of the images before i, off[n] = all blocks (one block of threads)
+__global__ __launch_bounds__(kThreads) void jpeg_offsets_kernel(const io_jpeg_desc* __restrict__ desc, int n,
+                                                                unsigned long long* __restrict__ off) {
+    __shared__ unsigned long long s[kThreads];
+    const int tid = threadIdx.x;
+    unsigned long long carry = 0;
+    for (int base = 0; base < n; base += kThreads) {             // block-uniform trip count
+        const int i = base + tid;
+        const unsigned long long w = i < n ? (unsigned long long)geometry(desc[i]).n_blocks : 0ull;
+        s[tid] = w;
+        __syncthreads();
+        for (int d = 1; d < kThreads; d <<= 1) {
+            const unsigned long long v = tid >= d ? s[tid - d] : 0ull;
+            __syncthreads();
+            s[tid] += v;
+            __syncthreads();
+        }
+        if (i < n) off[i] = carry + s[tid] - w;
+        carry += s[kThreads - 1];
+        __syncthreads();
+    }
+    if (tid == 0) off[n] = carry;
+}
+
+__global__ __launch_bounds__(64) void jpeg_tables_kernel(const io_jpeg_tables* __restrict__ tables, JpegHuff* __restrict__ huff) {
+    if (threadIdx.x >= 4) return;
+    const io_jpeg_tables& t = tables[blockIdx.x];
+    (void)jpeg_build_huff(t.huff_counts[threadIdx.x], t.huff_symbols[threadIdx.x], huff + 4 * blockIdx.x + threadIdx.x);
+}
+
+// the scan of image d with the derived tables at `set` (LDS or global: one copy of the loop per address space)
+__device__ __forceinline__ int decode_image(const io_jpeg_desc& d, const uint8_t* __restrict__ pool, const JpegHuff* set,
+                                            int16_t* __restrict__ coef) {
+    const Geo g = geometry(d);
+    JpegScan s;
+    s.data = pool + d.data_off;
+    s.nbytes = d.data_bytes;
+    s.n_mcu = g.mw * g.mh;
+    s.luma_blocks = d.hs * d.vs;
+    s.chroma = d.n_comp == 3 ? 1 : 0;
+    s.restart_interval = d.restart_interval;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        s.dc[c] = set + (d.dc[c] & 1);
+        s.ac[c] = set + 2 + (d.ac[c] & 1);
+    }
+    return jpeg_decode_scan(s, coef);
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(const uint8_t* __restrict__ pool,
+                                                                const JpegHuff* __restrict__ huff, int n_sets,
+                                                                const io_jpeg_desc* __restrict__ desc,
+                                                                const unsigned long long* __restrict__ off,
+                                                                int16_t* __restrict__ coef, int32_t* __restrict__ status,
+                                                                int n, int per_wave) {
+    // the derived tables of a batch with at most IO_JPEG_LDS_TABLE_SETS table sets are staged in LDS: a lookup is then an
+    // LDS read, which does not wait for the coefficient stores in flight as a global read does
+    __shared__ uint32_t s_huff[IO_JPEG_LDS_TABLE_SETS * 4 * sizeof(JpegHuff) / 4];
+    const bool staged = n_sets <= IO_JPEG_LDS_TABLE_SETS;        // block-uniform
+    if (staged) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(huff);
+        const int words = n_sets * 4 * (int)(sizeof(JpegHuff) / 4);
+        for (int k = threadIdx.x; k < words; k += kThreads) s_huff[k] = src[k];
+        __syncthreads();
+    }
+    const int wave = (int)((blockIdx.x * (unsigned)kThreads + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (lane >= per_wave) return;
+    const long i = (long)wave * per_wave + lane;
+    if (i >= n) return;
+    const io_jpeg_desc d = desc[i];
+    int16_t* dst = coef + 64 * (long)off[i];
+    int st;
+    if (staged) st = decode_image(d, pool, reinterpret_cast<const JpegHuff*>(s_huff) + 4 * (long)d.table_set, dst);
+    else st = decode_image(d, pool, huff + 4 * (long)d.table_set, dst);
+    status[i] = st;
+}
+
+// ---- stage 2 -----------------------------------------------------------------------------------------------------------
+constexpr int kNatOfZig[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+struct ZigOfNat {
+    int v[64];
+    constexpr ZigOfNat() : v() {
+        for (int k = 0; k < 64; ++k) v[kNatOfZig[k]] = k;
+    }
+};
+constexpr ZigOfNat kZigOfNat;
+
+// one 8-point pass of jidctint.c (CONST_BITS 13), without the descale
+__device__ __forceinline__ void idct8(const int* in, int stride, int* o) {
+    const int i0 = in[0], i1 = in[stride], i2 = in[2 * stride], i3 = in[3 * stride], i4 = in[4 * stride],
+              i5 = in[5 * stride], i6 = in[6 * stride], i7 = in[7 * stride];
+    int z1 = (i2 + i6) * 4433;
+    const int t2 = z1 + i6 * (-15137), t3 = z1 + i2 * 6270;
+    const int t0 = (i0 + i4) * 8192, t1 = (i0 - i4) * 8192;
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    int a0 = i7, a1 = i5, a2 = i3, a3 = i1;
+    z1 = a0 + a3;
+    int z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+    const int z5 = (z3 + z4) * 9633;
+    a0 *= 2446;
+    a1 *= 16819;
+    a2 *= 25172;
+    a3 *= 12299;
+    z1 *= -7373;
+    z2 *= -20995;
+    z3 = z3 * (-16069) + z5;
+    z4 = z4 * (-3196) + z5;
+    a0 += z1 + z3;
+    a1 += z2 + z4;
+    a2 += z2 + z3;
+    a3 += z1 + z4;
+    o[0] = t10 + a3;
+    o[1] = t11 + a2;
+    o[2] = t12 + a1;
+    o[3] = t13 + a0;
+    o[4] = t13 - a0;
+    o[5] = t12 - a1;
+    o[6] = t11 - a2;
+    o[7] = t10 - a3;
+}
+
+__device__ __forceinline__ unsigned clamp_byte(int v) { return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+__global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const io_jpeg_tables* __restrict__ tables,
+                                                             const io_jpeg_desc* __restrict__ desc,
+                                                             const unsigned long long* __restrict__ off,
+                                                             const int16_t* __restrict__ coef, uint8_t* __restrict__ planes,
+                                                             int n) {
+    const unsigned long long b = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
+    if (b >= off[n]) return;
+    int lo = 0, hi = n;                                          // the image with off[i] <= b < off[i + 1]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const io_jpeg_desc d = desc[lo];
+    const Geo g = geometry(d);
+    const long j = (long)(b - off[lo]);                          // block of the image in decode order
+    const int mcu = (int)(j / g.bpm), r = (int)(j - (long)mcu * g.bpm);
+    const int my = mcu / g.mw, mx = mcu - my * g.mw;
+    const int luma = d.hs * d.vs;
+    int comp, brow, bcol, stride;
+    uint8_t* plane = planes + 64 * (long)off[lo];
+    if (r < luma) {
+        comp = 0;
+        brow = my * d.vs + r / d.hs;
+        bcol = mx * d.hs + r % d.hs;
+        stride = g.ystride;
+    } else {
+        comp = 1 + (r - luma);
+        brow = my;
+        bcol = mx;
+        stride = g.cstride;
+        plane += g.ybytes + (comp - 1) * g.cbytes;
+    }
+    const uint16_t* q = tables[d.table_set].quant[d.quant[comp] & 3];
+    const int16_t* c = coef + 64 * (long)b;
+    int v[64], ws[64], o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {                                // a row of 8 coefficients and 8 table entries per load
+        const uint4 cw = *reinterpret_cast<const uint4*>(c + 8 * k);
+        const uint4 qw = *reinterpret_cast<const uint4*>(q + 8 * k);
+        const unsigned cc[4] = {cw.x, cw.y, cw.z, cw.w}, qq[4] = {qw.x, qw.y, qw.z, qw.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[8 * k + 2 * e] = (int)(int16_t)(cc[e] & 0xffffu);
+            v[8 * k + 2 * e + 1] = (int)(int16_t)(cc[e] >> 16);
+            ws[8 * k + 2 * e] = (int)(qq[e] & 0xffffu);           // ws holds the table (zig-zag order) until the first pass
+            ws[8 * k + 2 * e + 1] = (int)(qq[e] >> 16);
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < 64; ++p) v[p] *= ws[kZigOfNat.v[p]];
+#pragma unroll
+    for (int x = 0; x < 8; ++x) {
+        idct8(v + x, 8, o);
+#pragma unroll
+        for (int y = 0; y < 8; ++y) ws[8 * y + x] = (o[y] + (1 << 10)) >> 11;
+    }
+    uint8_t* dst = plane + (long)brow * 8 * stride + bcol * 8;
+#pragma unroll
+    for (int y = 0; y < 8; ++y) {
+        idct8(ws + 8 * y, 1, o);
+        unsigned w0 = 0, w1 = 0;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            w0 |= clamp_byte(((o[x] + (1 << 17)) >> 18) + 128) << (8 * x);
+            w1 |= clamp_byte(((o[x + 4] + (1 << 17)) >> 18) + 128) << (8 * x);
+        }
+        uint32_t* row = reinterpret_cast<uint32_t*>(dst + (long)y * stride);   // plane rows are multiples of 8 bytes
+        row[0] = w0;
+        row[1] = w1;
+    }
+}
+
+// ---- stage 3 -----------------------------------------------------------------------------------------------------------
+// the chroma sample of output pixel (y, x): triangle filter over the cw x ch REAL samples of the plane
+__device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, int stride, int cw, int ch, int hs, int vs, int y,
+                                         int x) {
+    if (hs == 1) return p[(long)y * stride + x];
+    const int cx = x >> 1;
+    if (cw <= 2) return p[(long)(vs == 2 ? y >> 1 : y) * stride + cx];    // libjpeg filters only planes wider than two samples
+    const int ox = (x & 1) ? (cx + 1 < cw ? cx + 1 : cw - 1) : (cx > 0 ? cx - 1 : 0);
+    if (vs == 1) {
+        const uint8_t* row = p + (long)y * stride;
+        return (3 * row[cx] + row[ox] + ((x & 1) ? 2 : 1)) >> 2;
+    }
+    const int cy = y >> 1;
+    const int fy = (y & 1) ? (cy + 1 < ch ? cy + 1 : ch - 1) : (cy > 0 ? cy - 1 : 0);
+    const uint8_t* near = p + (long)cy * stride;
+    const uint8_t* far = p + (long)fy * stride;
+    const int t = 3 * near[cx] + far[cx], to = 3 * near[ox] + far[ox];
+    return (3 * t + to + ((x & 1) ? 7 : 8)) >> 4;
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_colour_kernel(const io_jpeg_desc* __restrict__ desc,
+                                                               const unsigned long long* __restrict__ off,
+                                                               const uint8_t* __restrict__ planes, uint8_t* __restrict__ out) {
+    const io_jpeg_desc d = desc[blockIdx.y];
+    const long nbytes = 3L * d.H * d.W;
+    uint8_t* dst = out + d.out_off;
+    const int head = (int)((uintptr_t)dst & 3);
+    const long nwords = (nbytes + head + 3) >> 2;                // aligned words that cover dst[0 .. nbytes)
+    if ((long)blockIdx.x * kChunkWords >= nwords) return;
+    const Geo g = geometry(d);
+    const uint8_t* yp = planes + 64 * (long)off[blockIdx.y];
+    const uint8_t* cbp = yp + g.ybytes;
+    const uint8_t* crp = cbp + g.cbytes;
+    const int cw = (d.W + d.hs - 1) / d.hs, ch = (d.H + d.vs - 1) / d.vs;
+#pragma unroll
+    for (int jj = 0; jj < kWordsPerThread; ++jj) {
+        const long w = (long)blockIdx.x * kChunkWords + jj * kThreads + threadIdx.x;
+        if (w >= nwords) break;
+        const long p0 = 4 * w - head;
+        unsigned word = 0;
+        long have = -1;                                          // the pixel whose colour is in rgb
+        unsigned rgb = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long p = p0 + k;
+            if (p < 0 || p >= nbytes) continue;
+            const unsigned pix = (unsigned)p / 3u, c = (unsigned)p - 3u * pix;     // 3 H W < 2^31
+            if ((long)pix != have) {
+                have = pix;
+                const int y = (int)(pix / (unsigned)d.W), x = (int)(pix - (unsigned)y * (unsigned)d.W);
+                const int Y = yp[(long)y * g.ystride + x];
+                if (d.n_comp == 3) {
+                    const int cb = chroma_at(cbp, g.cstride, cw, ch, d.hs, d.vs, y, x) - 128;
+                    const int cr = chroma_at(crp, g.cstride, cw, ch, d.hs, d.vs, y, x) - 128;
+                    const unsigned R = clamp_byte(Y + ((91881 * cr + 32768) >> 16));
+                    const unsigned G = clamp_byte(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+                    const unsigned B = clamp_byte(Y + ((116130 * cb + 32768) >> 16));
+                    rgb = R | (G << 8) | (B << 16);
+                } else {
+                    rgb = (unsigned)Y * 0x010101u;
+                }
+            }
+            word |= ((rgb >> (8 * c)) & 0xffu) << (8 * k);
+        }
+        if (p0 >= 0 && p0 + 4 <= nbytes) {
+            *reinterpret_cast<uint32_t*>(dst + p0) = word;
+        } else {                                                 // first / last word of an image: bytes outside it are not ours
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (p0 + k >= 0 && p0 + k < nbytes) dst[p0 + k] = (uint8_t)(word >> (8 * k));
+        }
+    }
+}
+
+struct JpegPlan {
+    long total_blocks, max_words;
+    int n_sets;
+    size_t off_bytes, huff_bytes, coef_bytes, plane_bytes;
+    double out_bytes;
+};
+
+// the checks that need no buffer; *plan filled on success
+int jpeg_check_desc(const io_jpeg_desc* desc, int n, JpegPlan* plan) {
+    IO_REQUIRE(n > 0 && desc, IO_ERR_SHAPE, "jpeg_decode: empty batch or null descriptor table (n=%d)", n);
+    IO_REQUIRE(n <= 65535, IO_ERR_SHAPE, "jpeg_decode: n=%d out of range (at most 65535 images per call)", n);
+    long blocks = 0, max_words = 0;
+    int n_sets = 0;
+    double out_bytes = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const io_jpeg_desc& d = desc[i];
+        IO_REQUIRE(d.H >= 1 && d.W >= 1 && d.H <= 65535 && d.W <= 65535 && 3L * d.H * d.W < (1L << 31), IO_ERR_SHAPE,
+                   "jpeg_decode: image %d has size %d x %d (need 1 <= H, W <= 65535 and 3 H W < 2^31)", i, d.H, d.W);
+        const bool gray = d.n_comp == 1 && d.hs == 1 && d.vs == 1;
+        const bool ycc = d.n_comp == 3 && ((d.hs == 1 && d.vs == 1) || (d.hs == 2 && (d.vs == 1 || d.vs == 2)));
+        IO_REQUIRE(gray || ycc, IO_ERR_SHAPE,
+                   "jpeg_decode: image %d has %d components with luma sampling %d x %d (1 with 1x1, or 3 with 1x1, 2x1, 2x2)", i,
+                   d.n_comp, d.hs, d.vs);
+        IO_REQUIRE(d.restart_interval >= 0, IO_ERR_SHAPE, "jpeg_decode: image %d has restart_interval=%d", i,
+                   d.restart_interval);
+        IO_REQUIRE(d.table_set >= 0 && d.table_set <= 65535, IO_ERR_SHAPE, "jpeg_decode: image %d names table set %d", i,
+                   d.table_set);
+        for (int c = 0; c < d.n_comp; ++c)
+            IO_REQUIRE(d.quant[c] < 4 && d.dc[c] < 2 && d.ac[c] < 2, IO_ERR_SHAPE,
+                       "jpeg_decode: image %d component %d names tables quant=%d dc=%d ac=%d (quant < 4, Huffman < 2)", i, c,
+                       d.quant[c], d.dc[c], d.ac[c]);
+        IO_REQUIRE(d.data_off >= 0 && d.data_bytes >= 0, IO_ERR_SHAPE, "jpeg_decode: image %d has a negative data range", i);
+        if (d.table_set + 1 > n_sets) n_sets = d.table_set + 1;
+        blocks += geometry(d).n_blocks;
+        IO_REQUIRE(blocks < (1L << 31), IO_ERR_SHAPE, "jpeg_decode: more than 2^31 blocks in one call");
+        const long words = (3L * d.H * d.W + 3 + 3) / 4;
+        if (words > max_words) max_words = words;
+        out_bytes += 3.0 * d.H * d.W;
+    }
+    plan->total_blocks = blocks;
+    plan->max_words = max_words;
+    plan->n_sets = n_sets;
+    plan->off_bytes = ((size_t)(n + 1) * sizeof(unsigned long long) + 15) / 16 * 16;
+    plan->huff_bytes = (size_t)n_sets * 4 * sizeof(JpegHuff);
+    plan->coef_bytes = (size_t)blocks * 128;
+    plan->plane_bytes = (size_t)blocks * 64;
+    plan->out_bytes = out_bytes;
+    return IO_OK;
+}
+
+}  // namespace
+
+extern "C" int io_jpeg_set_images_per_wave(int images) {
+    IO_REQUIRE(images >= 1 && images <= 64, IO_ERR_SHAPE, "jpeg: images per wave %d (1..64)", images);
+    g_images_per_wave.store(images);
+    return IO_OK;
+}
+extern "C" int io_jpeg_get_images_per_wave(void) { return g_images_per_wave.load(); }
+extern "C" int io_jpeg_lds_table_sets(void) { return IO_JPEG_LDS_TABLE_SETS; }
+
+extern "C" size_t io_jpeg_workspace_bytes(const io_jpeg_desc* desc_host, int n) {
+    JpegPlan plan;
+    if (jpeg_check_desc(desc_host, n, &plan) != IO_OK) return 0;
+    return plan.off_bytes + plan.huff_bytes + plan.coef_bytes + plan.plane_bytes;
+}
+
+extern "C" int io_jpeg_decode_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev,
+                                 const io_jpeg_tables* tables_host, size_t tables_bytes, const io_jpeg_desc* desc_dev,
+                                 const io_jpeg_desc* desc_host, int n, uint8_t* out, size_t out_bytes, void* workspace,
+                                 size_t workspace_bytes, int32_t* status_dev, hipStream_t st) {
+    IO_REQUIRE(pool_dev && tables_dev && tables_host && desc_dev && out && workspace && status_dev, IO_ERR_SHAPE,
+               "jpeg_decode: null pointer");
+    JpegPlan plan;
+    const int rc = jpeg_check_desc(desc_host, n, &plan);
+    if (rc != IO_OK) return rc;
+    IO_REQUIRE((size_t)plan.n_sets * sizeof(io_jpeg_tables) <= tables_bytes, IO_ERR_SHAPE,
+               "jpeg_decode: table set %d outside the %zu table bytes", plan.n_sets - 1, tables_bytes);
+    for (int s = 0; s < plan.n_sets; ++s) {
+        JpegHuff h;
+        for (int t = 0; t < 4; ++t)
+            IO_REQUIRE(jpeg_build_huff(tables_host[s].huff_counts[t], tables_host[s].huff_symbols[t], &h), IO_ERR_SHAPE,
+                       "jpeg_decode: table set %d, Huffman table %d: the code lengths form no prefix code of at most 256 symbols",
+                       s, t);
+    }
+    for (int i = 0; i < n; ++i) {
+        const io_jpeg_desc& d = desc_host[i];
+        IO_REQUIRE((size_t)d.data_off <= pool_bytes && (size_t)d.data_bytes <= pool_bytes - (size_t)d.data_off, IO_ERR_SHAPE,
+                   "jpeg_decode: image %d data outside the byte pool", i);
+        const size_t nb = 3 * (size_t)d.H * (size_t)d.W;
+        IO_REQUIRE(d.out_off >= 0 && (size_t)d.out_off <= out_bytes && nb <= out_bytes - (size_t)d.out_off, IO_ERR_SHAPE,
+                   "jpeg_decode: image %d output outside the output buffer", i);
+    }
+    const size_t need = plan.off_bytes + plan.huff_bytes + plan.coef_bytes + plan.plane_bytes;
+    IO_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)tables_dev & 15) == 0 && ((uintptr_t)desc_dev & 7) == 0,
+               IO_ERR_SHAPE, "jpeg_decode: workspace and tables must be 16-byte aligned, descriptors 8-byte aligned");
+    IO_REQUIRE(workspace_bytes >= need, IO_ERR_WORKSPACE, "jpeg_decode: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    unsigned long long* off = reinterpret_cast<unsigned long long*>(ws);
+    JpegHuff* huff = reinterpret_cast<JpegHuff*>(ws + plan.off_bytes);
+    int16_t* coef = reinterpret_cast<int16_t*>(ws + plan.off_bytes + plan.huff_bytes);
+    uint8_t* planes = ws + plan.off_bytes + plan.huff_bytes + plan.coef_bytes;
+    const hipError_t e = hipMemsetAsync(coef, 0, plan.coef_bytes, st);
+    IO_REQUIRE(e == hipSuccess, IO_ERR_LAUNCH, "jpeg_decode: clearing the coefficients: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(jpeg_offsets_kernel, dim3(1), dim3(kThreads), 0, st, desc_dev, n, off);
+    hipLaunchKernelGGL(jpeg_tables_kernel, dim3(plan.n_sets), dim3(64), 0, st, tables_dev, huff);
+    const int per_wave = g_images_per_wave.load();
+    {
+        IoProfScope prof(IO_PROF_JPEG_ENTROPY, 0.0, (double)pool_bytes + (double)plan.coef_bytes, st);
+        const int waves = io_cdiv(n, per_wave);
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(io_cdiv(waves, kThreads / 64)), dim3(kThreads), 0, st, pool_dev, huff,
+                           plan.n_sets, desc_dev, off, coef, status_dev, n, per_wave);
+    }
+    {
+        IoProfScope prof(IO_PROF_JPEG_IDCT, 0.0, (double)plan.coef_bytes + (double)plan.plane_bytes, st);
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3(io_cdiv(plan.total_blocks, kThreads)), dim3(kThreads), 0, st, tables_dev,
+                           desc_dev, off, coef, planes, n);
+    }
+    {
+        IoProfScope prof(IO_PROF_JPEG_COLOUR, 0.0, (double)plan.plane_bytes + plan.out_bytes, st);
+        hipLaunchKernelGGL(jpeg_colour_kernel, dim3(io_cdiv(plan.max_words, kChunkWords), n), dim3(kThreads), 0, st, desc_dev,
+                           off, planes, out);
+    }
+    return io_check_launch("jpeg_decode");
+}

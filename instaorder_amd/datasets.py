@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .jpeg import is_jpeg
 from .rle import is_encoded
 
 INTER_LINEAR, INTER_CUBIC, INTER_CUBIC_F64 = 1, 2, 3     # io_pair_desc.interp
@@ -86,6 +87,7 @@ class PairRenderer(object):
         self._pinned = [None, None]
         self._events = [None, None]
         self._turn = 0
+        self._status = [None, None]  # per staging slot: (pinned int32 status words of the JPEG decode, the images' names)
         self.last_upload = None      # bytes the last render() sent to the device: images / masks (or run tables, vertices) / descriptors
 
     def _staging(self, nbytes):
@@ -94,9 +96,27 @@ class PairRenderer(object):
         self._turn ^= 1
         if self._events[k] is not None:
             self._events[k].synchronize()
+            self._check_slot(k)
         if self._pinned[k] is None or self._pinned[k].numel() < nbytes:
             self._pinned[k] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
         return k, self._pinned[k]
+
+    def _check_slot(self, k):
+        """the JPEG status words of the batch that used staging slot k (its event has been waited for)"""
+        if self._status[k] is not None:
+            words, images = self._status[k]
+            self._status[k] = None
+            from . import jpeg
+            jpeg.raise_for_status(words.numpy(), images)
+
+    def check_status(self):
+        """Waits for the batches still in flight and raises RuntimeError naming a JPEG image that did not decode.  render()
+        reports such an image by itself when its staging slot comes round again, two batches later; this is for the end
+        of a run (``BatchPrefetcher`` calls it)."""
+        for k in (0, 1):
+            if self._status[k] is not None:
+                self._events[k].synchronize()
+                self._check_slot(k)
 
     @staticmethod
     def _check_item(images, masks, ii, load_rgb):
@@ -144,13 +164,13 @@ class PairRenderer(object):
         return rgb, m1, m2
 
     def render(self, images, masks, items, load_rgb=True):
-        """images: list of uint8 [H,W,3] arrays (entries may be None when load_rgb is False); masks: list of uint8
+        """images: list of uint8 [H,W,3] arrays or ``jpeg.JpegImage`` (entries may be None when load_rgb is False); masks: list of uint8
         [n,H,W] arrays, ``rle.RLEMasks`` or ``poly.PolyMasks``, one per image; items: list of (image_index, idx1, idx2,
         (x, y, w, h), interp, flip)."""
         P = len(items)
         if P == 0:
             raise ValueError("PairRenderer.render: empty batch")
-        if any(is_encoded(m) for m in masks):
+        if any(is_encoded(m) for m in masks) or (load_rgb and any(is_jpeg(im) for im in images)):
             return self._render_rle(images, masks, items, load_rgb)
         # arena layout: every referenced image once, every referenced mask once (16-byte aligned)
         off, cursor = {}, 0
@@ -183,14 +203,16 @@ class PairRenderer(object):
         return self._launch(dev.data_ptr(), nbytes, dev.data_ptr() + nbytes, desc, load_rgb, stream)
 
     def _render_rle(self, images, masks, items, load_rgb):
-        """render() for a batch in which at least one image carries ``rle.RLEMasks`` or ``poly.PolyMasks``.  The arena
-        lives on the device and only part of it is uploaded: one device buffer [images and dense masks | run tables |
-        decode descriptors | vertices | part and mask descriptors | pair descriptors | decoded masks | polygon workspace],
-        of which everything before the decoded masks comes through the pinned staging buffer in one copy.  One
-        ``io_rle_decode_u8`` launch fills the slot of every referenced run-length mask and one ``io_poly_fill_u8`` call the
-        slot of every referenced polygon instance, then ``io_pair_planes_u8_hw`` runs on the arena as it does for dense
-        masks.  (A batch without polygons has empty polygon regions: the layout of the run-length path as it was.)"""
-        from . import poly, rle
+        """render() for a batch in which at least one image carries ``rle.RLEMasks`` or ``poly.PolyMasks``, or is a
+        ``jpeg.JpegImage``.  The arena lives on the device and only part of it is uploaded: one device buffer [array images
+        and dense masks | run tables | decode descriptors | vertices | part and mask descriptors | entropy bytes | JPEG
+        tables and descriptors | pair descriptors | decoded masks and images | polygon workspace | JPEG workspace and
+        status], of which everything before the decoded part comes through the pinned staging buffer in one copy.  One
+        ``io_rle_decode_u8`` launch fills the slot of every referenced run-length mask, one ``io_poly_fill_u8`` call the
+        slot of every referenced polygon instance and one ``io_jpeg_decode_u8`` call the slot of every referenced JPEG
+        image, then ``io_pair_planes_u8_hw`` runs on the arena as it does for dense arrays.  (A batch without polygons or
+        JPEG images has empty regions for them: the layout of the run-length path as it was.)"""
+        from . import jpeg, poly, rle
         P = len(items)
         up, dec = {}, {}                     # key -> offset inside its region
         cursors = {id(up): 0, id(dec): 0}
@@ -208,12 +230,16 @@ class PairRenderer(object):
         for ii, i1, i2, box, interp, flip in items:
             n, H, W = self._check_item(images, masks, ii, load_rgb)
             region = dec if is_encoded(masks[ii]) else up
-            keys.append((place(up, ("img", ii), H * W * 3) if load_rgb else None, region,
+            keys.append((place(dec if is_jpeg(images[ii]) else up, ("img", ii), H * W * 3) if load_rgb else None, region,
                          place(region, ("m", ii, range(n)[int(i1)]), H * W),
                          place(region, ("m", ii, range(n)[int(i2)]), H * W)))
         # an instance of the decoded region is a run-length code (of RLEMasks, or one inside PolyMasks) or a polygon
         refs = [(key, (masks[key[1]], key[2]) if isinstance(masks[key[1]], rle.RLEMasks) else masks[key[1]].rle_ref(key[2]))
-                for key in dec]
+                for key in dec if key[0] == "m"]
+        jp_keys = [key for key in dec if key[0] == "img"]
+        jpool, jtabs, jdesc = jpeg.descriptors([images[k[1]] for k in jp_keys], [0] * len(jp_keys)) if jp_keys else (
+            np.zeros(0, np.uint8), np.zeros(0, np.uint8), ())
+        jdbytes = C.sizeof(jdesc) if jp_keys else 0
         dec_keys = [key for key, ref in refs if ref is not None]
         pol_keys = [key for key, ref in refs if ref is None]
         ends, rdesc = rle.descriptors([ref for key, ref in refs if ref is not None], [0] * len(dec_keys))
@@ -225,7 +251,10 @@ class PairRenderer(object):
         vt_at = rd_at + (C.sizeof(rdesc) + 15) // 16 * 16
         pp_at = vt_at + (verts.nbytes + 15) // 16 * 16
         pm_at = pp_at + (pbytes[0] + 15) // 16 * 16
-        pd_at = pm_at + (pbytes[1] + 15) // 16 * 16
+        jp_at = pm_at + (pbytes[1] + 15) // 16 * 16
+        jt_at = jp_at + (jpool.size + 15) // 16 * 16
+        jd_at = jt_at + (jtabs.size + 15) // 16 * 16
+        pd_at = jd_at + (jdbytes + 15) // 16 * 16
         dec_at = pd_at + (C.sizeof(desc) + 15) // 16 * 16             # = the bytes that are uploaded
         nbytes = dec_at + max(cursors[id(dec)], 16)
         ws_at = (nbytes + 15) // 16 * 16
@@ -234,10 +263,16 @@ class PairRenderer(object):
             rdesc[k].out_off = dec_at + dec[key]
         for k, key in enumerate(pol_keys):
             pmasks[k].out_off = dec_at + dec[key]
+        for k, key in enumerate(jp_keys):
+            jdesc[k].out_off = dec_at + dec[key]
+        jws_at = (ws_at + ws_bytes + 15) // 16 * 16
+        jws_bytes = jpeg.workspace_bytes(jdesc) if jp_keys else 0
+        st_at = jws_at + jws_bytes
         for k, ((ii, i1, i2, box, interp, flip), (kimg, region, k1, k2)) in enumerate(zip(items, keys)):
             base = dec_at if region is dec else 0
             _, H, W = masks[ii].shape
-            self._fill_desc(desc[k], up[kimg] if load_rgb else 0, base + region[k1], base + region[k2], H, W, box, interp,
+            image_off = 0 if not load_rgb else (dec_at + dec[kimg] if kimg in dec else up[kimg])
+            self._fill_desc(desc[k], image_off, base + region[k1], base + region[k2], H, W, box, interp,
                             flip)
         slot, stage = self._staging(dec_at)
         host = stage.numpy()
@@ -248,14 +283,31 @@ class PairRenderer(object):
             host[vt_at:vt_at + verts.nbytes] = verts.view(np.uint8).reshape(-1)
             host[pp_at:pp_at + pbytes[0]] = np.frombuffer(pparts, dtype=np.uint8)
             host[pm_at:pm_at + pbytes[1]] = np.frombuffer(pmasks, dtype=np.uint8)
+        if jp_keys:
+            host[jp_at:jp_at + jpool.size] = jpool
+            host[jt_at:jt_at + jtabs.size] = jtabs
+            host[jd_at:jd_at + jdbytes] = np.frombuffer(jdesc, dtype=np.uint8)
         host[pd_at:pd_at + C.sizeof(desc)] = np.frombuffer(desc, dtype=np.uint8)
-        dev = torch.empty(ws_at + ws_bytes if pol_keys else nbytes, dtype=torch.uint8, device=self.device)
+        dev = torch.empty(st_at + 4 * len(jp_keys) if jp_keys else (ws_at + ws_bytes if pol_keys else nbytes),
+                          dtype=torch.uint8, device=self.device)
         dev[:dec_at].copy_(stage[:dec_at], non_blocking=True)
         stream = torch.cuda.current_stream(self.device)
         self._upload_done(slot, stream)
-        self.last_upload = dict(images=sent["img"], masks=sent["m"] + ends.nbytes + verts.nbytes,
-                                descriptors=C.sizeof(rdesc) + sum(pbytes) + C.sizeof(desc), total=dec_at)
+        self.last_upload = dict(images=sent["img"] + jpool.size + jtabs.size, masks=sent["m"] + ends.nbytes + verts.nbytes,
+                                descriptors=C.sizeof(rdesc) + sum(pbytes) + jdbytes + C.sizeof(desc), total=dec_at)
         base = dev.data_ptr()
+        if jp_keys:
+            rc = _lib.lib().io_jpeg_decode_u8(C.c_void_p(base + jp_at), C.c_size_t(jpool.size), C.c_void_p(base + jt_at),
+                                              jtabs.ctypes.data_as(C.c_void_p), C.c_size_t(jtabs.size), C.c_void_p(base + jd_at),
+                                              C.cast(jdesc, C.c_void_p), len(jp_keys), C.c_void_p(base), C.c_size_t(nbytes),
+                                              C.c_void_p(base + jws_at), C.c_size_t(jws_bytes), C.c_void_p(base + st_at),
+                                              C.c_void_p(stream.cuda_stream))
+            _lib.check(rc, "io_jpeg_decode_u8")
+            # the status words follow the batch to pinned memory; they are read when this staging slot comes round again
+            words = torch.empty(len(jp_keys), dtype=torch.int32).pin_memory()
+            words.copy_(dev[st_at:st_at + 4 * len(jp_keys)].view(torch.int32), non_blocking=True)
+            self._status[slot] = (words, [images[k[1]] for k in jp_keys])
+            self._upload_done(slot, stream)
         if dec_keys:
             rc = _lib.lib().io_rle_decode_u8(C.c_void_p(base + tab_at), C.c_size_t(ends.size), C.c_void_p(base + rd_at),
                                              C.cast(rdesc, C.c_void_p), len(dec_keys), C.c_void_p(base),
@@ -319,7 +371,8 @@ class _Batches(object):
             if key not in seen:
                 seen[key] = len(masks)
                 masks.append(p["modal"])
-                images.append(np.asarray(self.load_image(p["image_fn"])) if load_rgb else None)
+                img = self.load_image(p["image_fn"]) if load_rgb else None
+                images.append(img if img is None or is_jpeg(img) else np.asarray(img))
             items.append((seen[key], p["idx1"], p["idx2"], p["box"], p["interp"], p["flip"]))
         return self.renderer.render(images, masks, items, load_rgb=load_rgb)
 
@@ -494,6 +547,9 @@ class BatchPrefetcher(object):
                         ev = torch.cuda.Event()
                         ev.record(self._stream)
                         self._q.put((out, ev))
+                    renderer = getattr(self.batches, "_renderer", None)
+                    if renderer is not None:
+                        renderer.check_status()        # a JPEG image of the last two batches that did not decode
             except BaseException as e:          # surfaced on the consumer side
                 self._err = e
             self._q.put(None)

@@ -86,7 +86,7 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
                 modal = modal.to_dense()
         elif kind != "SupDepthOccOrderDataset" and data_cfg.get("use_category", False):
             modal = modal * category[:, None, None]
-        image = None if (callable(order_method) or order_method in ("area", "yaxis")) else np.asarray(load_image(image_fn))
+        image = None if (callable(order_method) or order_method in ("area", "yaxis")) else _loaded(load_image(image_fn))
         boxes = expand_bbox(bboxes, data_cfg["enlarge_box"])
         gt_occ = gt_dep = None
         if want_occ:
@@ -162,9 +162,15 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
     return out
 
 
+def _loaded(image):
+    """a ``jpeg.JpegImage`` goes to the renderer as it is"""
+    from .jpeg import is_jpeg
+    return image if is_jpeg(image) else np.asarray(image)
+
+
 def _identity_inputs(image, modal, size):
     if image.shape[0] != image.shape[1] or image.shape[0] != size:
         raise NotImplementedError("InstaDepthNet_od evaluation: patch_or_image='resize', or square images of the network size")
     from .synthetic import image_mode_inputs
-    rgb, masks = image_mode_inputs(image, modal, size)
+    rgb, masks = image_mode_inputs(infer.host_image(image, "cuda"), modal, size)
     return torch.from_numpy(rgb), torch.from_numpy(masks)

@@ -309,6 +309,27 @@ def _host_masks(masks, mr):
     return masks.to_dense() if mr is None and _is_rle(masks) else masks
 
 
+def _device_image(image):
+    """what the renderer takes: a ``jpeg.JpegImage`` as it is (decoded on the device), anything else as a uint8 array"""
+    from .jpeg import is_jpeg
+    return image if is_jpeg(image) else np.ascontiguousarray(image.astype(np.uint8))
+
+
+def host_image(image, dev):
+    """uint8 [H,W,3] on the host for the paths that need pixels there; a ``jpeg.JpegImage`` is decoded on the device"""
+    from . import jpeg
+    return jpeg.decode([image], dev)[0].cpu().numpy() if jpeg.is_jpeg(image) else image
+
+
+def _render_checked(r, image, *args, **kw):
+    """render, and for a JPEG image wait for its status: a file that does not decode must not yield an order matrix"""
+    from .jpeg import is_jpeg
+    out = r.render([image], *args, **kw)
+    if is_jpeg(image):
+        r.check_status()
+    return out
+
+
 def _preprocess_pairs(model, image, inmodal, bboxes, pair_list, patch_or_image, input_size):
     """The per-pair pre-processing of inference.py:449-482 on the device (datasets.PairRenderer): 'patch' = square
     crop around the pair (zero padded), INTER_CUBIC; 'image' = zero padding to a square, INTER_LINEAR; masks
@@ -320,7 +341,7 @@ def _preprocess_pairs(model, image, inmodal, bboxes, pair_list, patch_or_image, 
         raise ValueError("patch_or_image=%r: one of 'patch', 'image', 'resize', 'orig'" % (patch_or_image,))
     dev = model.net.flat_params.device
     modal = inmodal if _is_rle(inmodal) else np.ascontiguousarray(inmodal.astype(np.uint8))
-    image = np.ascontiguousarray(image.astype(np.uint8))
+    image = _device_image(image)
     _, hh, ww = modal.shape
     items = []
     for i, j in pair_list:
@@ -332,7 +353,7 @@ def _preprocess_pairs(model, image, inmodal, bboxes, pair_list, patch_or_image, 
             hw = int(max(hh, ww))
             box = (-((hw - ww) // 2), -((hw - hh) // 2), hw, hw)
             items.append((0, i, j, box, datasets.INTER_LINEAR, False))
-    return _renderer(dev, input_size).render([image], [modal], items)
+    return _render_checked(_renderer(dev, input_size), image, [modal], items)
 
 
 def _renderer(dev, input_size):
@@ -357,11 +378,11 @@ def resize_mode_inputs(dev, image, inmodal, input_size):
 def _whole_image_inputs(dev, image, inmodal, size):
     from . import datasets
     modal = inmodal if _is_rle(inmodal) else np.ascontiguousarray(inmodal.astype(np.uint8))
-    image = np.ascontiguousarray(image.astype(np.uint8))
+    image = _device_image(image)
     n, hh, ww = modal.shape
     box = (0, 0, ww, hh)
     r = _renderer(dev, size)
-    rgb, _, _ = r.render([image], [modal], [(0, 0, 0, box, datasets.INTER_CUBIC_F64, False)])
+    rgb, _, _ = _render_checked(r, image, [modal], [(0, 0, 0, box, datasets.INTER_CUBIC_F64, False)])
     _, m, _ = r.render([image], [modal], [(0, i, i, box, datasets.INTER_CUBIC_F64, False) for i in range(n)],
                        load_rgb=False)
     return rgb, m[:, 0]
@@ -531,7 +552,7 @@ def infer_order_sup_depth(model, image, inmodal, bboxes, pairs, method, patch_or
             rgb, masks = orig_mode_inputs(dev, image, inmodal)
         elif patch_or_image == "image" and image.shape[0] == image.shape[1] == input_size:
             from .synthetic import image_mode_inputs
-            rgb, masks = image_mode_inputs(image, _host_masks(inmodal, None), input_size)
+            rgb, masks = image_mode_inputs(host_image(image, dev), _host_masks(inmodal, None), input_size)
             rgb, masks = torch.from_numpy(rgb).to(dev), torch.from_numpy(masks)
         else:
             raise NotImplementedError("midas_pretrained: patch_or_image='resize' / 'orig', or 'image' on square images of "
@@ -569,7 +590,8 @@ def infer_order_sup_depth(model, image, inmodal, bboxes, pairs, method, patch_or
             rgb, masks = rgb.cpu().numpy(), masks.cpu().numpy()
     elif patch_or_image == "image" and image.shape[0] == image.shape[1] == input_size:
         from .synthetic import image_mode_inputs
-        rgb, masks = image_mode_inputs(image, _host_masks(inmodal, None), input_size)
+        rgb, masks = image_mode_inputs(host_image(image, next(model.model.parameters()).device),
+                                       _host_masks(inmodal, None), input_size)
     else:
         raise NotImplementedError("InstaDepthNet inference: patch_or_image='resize' / 'orig', or 'image' on square images "
                                   "of the network size (per-pair crops would run the MiDaS encoder once per pair)")
