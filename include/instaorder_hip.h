@@ -748,6 +748,28 @@ int io_jpeg_decode_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_
                       size_t workspace_bytes, int32_t* status_dev, hipStream_t stream);
 /* 0 = descriptors the call would refuse (io_last_error_string says why); never 0 for valid ones */
 size_t io_jpeg_workspace_bytes(const io_jpeg_desc* desc_host, int n);
+/* The same decode with stage (1) on many lanes per image (csrc/jpeg_sync.h; opt-in, io_jpeg_decode_u8 is unchanged): one
+ * 256-thread block per image cuts the entropy-coded bytes into subsequences of subseq_bytes (a multiple of 8 from 16 to
+ * 4096), decodes them side by side from guessed states and repeats, in at most max_rounds (1..65535) synchronous rounds,
+ * the subsequences whose entry state changed; RSTn markers are hard synchronisation points.  A clean image -- converged,
+ * no violation of the code inside its blocks, restart markers in order, all blocks present -- gets its coefficients from
+ * one more pass over its subsequences; every other image is decoded by the one-lane loop of io_jpeg_decode_u8, launched
+ * behind with a per-image predicate in device memory (no host wait).  Output bytes and status words are those of
+ * io_jpeg_decode_u8 for every stream.  info_dev (n int32, may be NULL): bits 0-15 the rounds run, bit 16 the image did
+ * not converge within max_rounds, bit 17 it converged but was not clean; either bit: decoded by the one-lane loop.
+ * A damaged stream can be slow to say so: behind a marker other than RSTn every subsequence exits where it entered, the
+ * changed entry moves on by one subsequence per round, and the image spends min(subsequences, max_rounds) rounds before it
+ * falls back -- with bit 16 if max_rounds came first, else bit 17.  Pixels and status do not depend on which.
+ *   Validation as for io_jpeg_decode_u8, and IO_ERR_SHAPE for subseq_bytes or max_rounds out of range.  Workspace
+ * (io_jpeg_par_workspace_bytes; 0: refused): that of io_jpeg_decode_u8 plus 8 bytes and a word per image and 64 bytes per
+ * subsequence.  Nothing is kept between calls.  Whatever the bytes are, a round makes at most 8 * subseq_bytes + 32 passes
+ * per subsequence, reads stay inside the image's data range and stores inside its coefficient range. */
+size_t io_jpeg_par_workspace_bytes(const io_jpeg_desc* desc_host, int n, int subseq_bytes);
+int io_jpeg_decode_par_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev,
+                          const io_jpeg_tables* tables_host, size_t tables_bytes, const io_jpeg_desc* desc_dev,
+                          const io_jpeg_desc* desc_host, int n, uint8_t* out, size_t out_bytes, void* workspace,
+                          size_t workspace_bytes, int32_t* status_dev, int subseq_bytes, int max_rounds, int32_t* info_dev,
+                          hipStream_t stream);
 /* images one wave64 of the entropy stage decodes side by side, one lane each (1..64, default 1; a tuning knob, process-global) */
 int io_jpeg_set_images_per_wave(int images);
 int io_jpeg_get_images_per_wave(void);

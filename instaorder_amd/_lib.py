@@ -134,6 +134,9 @@ SIGNATURES = {
     # workspace_bytes, status_dev, stream
     "io_jpeg_decode_u8": (_I, [_P, _Z, _P, _P, _Z, _P, _P, _I, _P, _Z, _P, _Z, _P, _P]),
     "io_jpeg_workspace_bytes": (_Z, [_P, _I]),
+    # the arguments of io_jpeg_decode_u8 up to status_dev, then subseq_bytes, max_rounds, info_dev, stream
+    "io_jpeg_decode_par_u8": (_I, [_P, _Z, _P, _P, _Z, _P, _P, _I, _P, _Z, _P, _Z, _P, _I, _I, _P, _P]),
+    "io_jpeg_par_workspace_bytes": (_Z, [_P, _I, _I]),
     "io_jpeg_set_images_per_wave": (_I, [_I]),
     "io_jpeg_get_images_per_wave": (_I, []),
     "io_jpeg_lds_table_sets": (_I, []),

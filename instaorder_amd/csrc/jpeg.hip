@@ -14,12 +14,17 @@
 //   3. jpeg_colour_kernel    as rle_decode_kernel: a thread owns one aligned 4-byte word of the output, computes the (at
 //                            most two) pixels its bytes belong to -- triangle upsampling of the chroma planes over their
 //                            REAL width and height, 16-bit fixed-point YCbCr -> RGB -- and stores the word once.
+//   1p. jpeg_sync_kernel     (io_jpeg_decode_par_u8 only) stage 1 on MANY lanes per image: one 256-thread block per image runs the
+//      jpeg_fallback_kernel  self-synchronising scheme of jpeg_sync.h -- threads stride over the subsequences of the scan, the
+//                            rounds loop inside the kernel -- and stores the coefficients of a clean image; every other
+//                            image is decoded by the one-lane loop of stage 1, launched behind it with a per-image predicate.
 // All arithmetic is 32-bit two's complement, which holds every intermediate of a stream an encoder made from 8-bit samples.
 //
 // Safety does not depend on the pool or table bytes: see jpeg_entropy.h for stage 1; stages 2 and 3 read and write only
 // addresses that follow from the descriptors the host validated, and every sample is clamped to a byte before it is stored.
 #include "io_common.h"
 #include "jpeg_entropy.h"
+#include "jpeg_sync.h"
 
 #include <atomic>
 
@@ -125,6 +130,130 @@ __global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(const uint8_t* _
     if (lane >= per_wave) return;
     const long i = (long)wave * per_wave + lane;
     if (i >= n) return;
+    const io_jpeg_desc d = desc[i];
+    int16_t* dst = coef + 64 * (long)off[i];
+    int st;
+    if (staged) st = decode_image(d, pool, reinterpret_cast<const JpegHuff*>(s_huff) + 4 * (long)d.table_set, dst);
+    else st = decode_image(d, pool, huff + 4 * (long)d.table_set, dst);
+    status[i] = st;
+}
+
+// ---- stage 1 on many lanes (jpeg_sync.h) --------------------------------------------------------------------------------
+// suboff[i] = subsequences of the images before i, suboff[n] = all of them (one block of threads)
+__global__ __launch_bounds__(kThreads) void jpeg_sub_offsets_kernel(const io_jpeg_desc* __restrict__ desc, int n, int subseq_bytes,
+                                                                    unsigned long long* __restrict__ suboff) {
+    __shared__ unsigned long long s[kThreads];
+    const int tid = threadIdx.x;
+    unsigned long long carry = 0;
+    for (int base = 0; base < n; base += kThreads) {             // block-uniform trip count
+        const int i = base + tid;
+        const unsigned long long w = i < n ? (unsigned long long)jpeg_sync_count(desc[i].data_bytes, subseq_bytes) : 0ull;
+        s[tid] = w;
+        __syncthreads();
+        for (int d = 1; d < kThreads; d <<= 1) {
+            const unsigned long long v = tid >= d ? s[tid - d] : 0ull;
+            __syncthreads();
+            s[tid] += v;
+            __syncthreads();
+        }
+        if (i < n) suboff[i] = carry + s[tid] - w;
+        carry += s[kThreads - 1];
+        __syncthreads();
+    }
+    if (tid == 0) suboff[n] = carry;
+}
+
+// One block per image; thread t owns the subsequences t, t + 256, ...  Every barrier is reached by all threads: the trip
+// counts of the strided loops differ per thread, the barriers stand outside them, and the rounds loop ends on a flag in LDS
+// that all threads read behind a barrier.  The records live in the workspace (64 bytes per subsequence, word-major).
+__global__ __launch_bounds__(kThreads) void jpeg_sync_kernel(const uint8_t* __restrict__ pool, const JpegHuff* __restrict__ huff,
+                                                             const io_jpeg_desc* __restrict__ desc,
+                                                             const unsigned long long* __restrict__ off,
+                                                             const unsigned long long* __restrict__ suboff,
+                                                             uint32_t* __restrict__ rec_all, int16_t* __restrict__ coef,
+                                                             int32_t* __restrict__ status, int32_t* __restrict__ fallback,
+                                                             int32_t* __restrict__ info, int subseq_bytes, int max_rounds) {
+    __shared__ uint32_t s_huff[4 * sizeof(JpegHuff) / 4];
+    __shared__ int s_changed[2];
+    __shared__ int s_live;
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const io_jpeg_desc d = desc[img];
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(huff + 4 * (long)d.table_set);
+        for (int k = tid; k < 4 * (int)(sizeof(JpegHuff) / 4); k += kThreads) s_huff[k] = src[k];
+        if (tid < 2) s_changed[tid] = 0;
+    }
+    const Geo g = geometry(d);
+    const JpegHuff* set = reinterpret_cast<const JpegHuff*>(s_huff);
+    JpegScan s;
+    s.data = pool + d.data_off;
+    s.nbytes = d.data_bytes;
+    s.n_mcu = g.mw * g.mh;
+    s.luma_blocks = d.hs * d.vs;
+    s.chroma = d.n_comp == 3 ? 1 : 0;
+    s.restart_interval = d.restart_interval;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        s.dc[c] = set + (d.dc[c] & 1);
+        s.ac[c] = set + 2 + (d.ac[c] & 1);
+    }
+    const int32_t nsub = jpeg_sync_count(d.data_bytes, subseq_bytes);
+    uint32_t* rec = rec_all + (size_t)JS_WORDS * suboff[img];
+    for (int32_t i = tid; i < nsub; i += kThreads) jpeg_sync_init_one(s, rec, nsub, i, subseq_bytes);
+    __syncthreads();
+    int rounds = 0;
+    bool converged = false;
+    for (int t = 1; t <= max_rounds; ++t) {                      // block-uniform: ends on s_changed, read behind a barrier
+        for (int32_t i = tid; i < nsub; i += kThreads) jpeg_sync_round_one(s, rec, nsub, i, subseq_bytes);
+        __syncthreads();
+        if (tid == 0) s_changed[(t + 1) & 1] = 0;                // last read before the barrier above, next written behind the one below
+        bool any = false;
+        for (int32_t i = tid; i < nsub; i += kThreads) any = jpeg_sync_entry_one(rec, nsub, i) || any;
+        if (any) atomicOr(&s_changed[t & 1], 1);
+        __syncthreads();
+        rounds = t;
+        if (!s_changed[t & 1]) {
+            converged = true;
+            break;
+        }
+    }
+    if (tid == 0) {
+        const int32_t live = converged ? jpeg_sync_finish(rec, nsub, g.n_blocks) : 0;
+        const int32_t word = rounds | (!converged ? JPEG_INFO_NOT_CONVERGED : (live == 0 ? JPEG_INFO_NOT_CLEAN : 0));
+        s_live = live;
+        fallback[img] = word >> 16;
+        if (info) info[img] = word;
+        if (live) status[img] = JPEG_STATUS_OK;
+    }
+    __syncthreads();
+    const int32_t live = s_live;
+    int16_t* dst = coef + 64 * (long)off[img];
+    for (int32_t i = tid; i < live; i += kThreads) jpeg_sync_write_one(s, rec, nsub, i, subseq_bytes, dst, g.n_blocks);
+}
+
+// jpeg_entropy_kernel with one image per wave, for the images jpeg_sync_kernel left: fallback[i] != 0
+__global__ __launch_bounds__(kThreads) void jpeg_fallback_kernel(const uint8_t* __restrict__ pool, const JpegHuff* __restrict__ huff,
+                                                                 int n_sets, const io_jpeg_desc* __restrict__ desc,
+                                                                 const unsigned long long* __restrict__ off,
+                                                                 int16_t* __restrict__ coef, int32_t* __restrict__ status,
+                                                                 const int32_t* __restrict__ fallback, int n) {
+    __shared__ uint32_t s_huff[IO_JPEG_LDS_TABLE_SETS * 4 * sizeof(JpegHuff) / 4];
+    constexpr int kWaves = kThreads / 64;
+    bool need = false;                                           // block-uniform: the block's images, read by every thread
+    for (int w = 0; w < kWaves; ++w) {
+        const long j = (long)blockIdx.x * kWaves + w;
+        if (j < n && fallback[j]) need = true;
+    }
+    if (!need) return;
+    const bool staged = n_sets <= IO_JPEG_LDS_TABLE_SETS;
+    if (staged) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(huff);
+        const int words = n_sets * 4 * (int)(sizeof(JpegHuff) / 4);
+        for (int k = threadIdx.x; k < words; k += kThreads) s_huff[k] = src[k];
+        __syncthreads();
+    }
+    const long i = (long)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if ((threadIdx.x & 63) != 0 || i >= n || !fallback[i]) return;
     const io_jpeg_desc d = desc[i];
     int16_t* dst = coef + 64 * (long)off[i];
     int st;
@@ -394,13 +523,34 @@ extern "C" size_t io_jpeg_workspace_bytes(const io_jpeg_desc* desc_host, int n) 
     return plan.off_bytes + plan.huff_bytes + plan.coef_bytes + plan.plane_bytes;
 }
 
-extern "C" int io_jpeg_decode_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev,
-                                 const io_jpeg_tables* tables_host, size_t tables_bytes, const io_jpeg_desc* desc_dev,
-                                 const io_jpeg_desc* desc_host, int n, uint8_t* out, size_t out_bytes, void* workspace,
-                                 size_t workspace_bytes, int32_t* status_dev, hipStream_t st) {
+namespace {
+
+// what the parallel entropy stage adds behind the sequential workspace: subsequence offsets, fallback words, records
+struct JpegParPlan {
+    long total_sub;
+    size_t suboff_bytes, fallback_bytes, rec_bytes;
+};
+
+int jpeg_check_par(const io_jpeg_desc* desc, int n, int subseq_bytes, JpegParPlan* par) {
+    IO_REQUIRE(subseq_bytes >= JPEG_SYNC_MIN_BYTES && subseq_bytes <= JPEG_SYNC_MAX_BYTES && subseq_bytes % 8 == 0, IO_ERR_SHAPE,
+               "jpeg_decode_par: subseq_bytes=%d (a multiple of 8 from %d to %d)", subseq_bytes, JPEG_SYNC_MIN_BYTES,
+               JPEG_SYNC_MAX_BYTES);
+    long total = 0;
+    for (int i = 0; i < n; ++i) total += jpeg_sync_count(desc[i].data_bytes, subseq_bytes);
+    par->total_sub = total;
+    par->suboff_bytes = ((size_t)(n + 1) * sizeof(unsigned long long) + 15) / 16 * 16;
+    par->fallback_bytes = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16;
+    par->rec_bytes = (size_t)total * JS_WORDS * sizeof(uint32_t);
+    return IO_OK;
+}
+
+// the checks of a decode call that need the buffers' sizes; the workspace size is left to the caller
+int jpeg_check_call(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev, const io_jpeg_tables* tables_host,
+                    size_t tables_bytes, const io_jpeg_desc* desc_dev, const io_jpeg_desc* desc_host, int n, uint8_t* out,
+                    size_t out_bytes, void* workspace, int32_t* status_dev, JpegPlan* planp) {
     IO_REQUIRE(pool_dev && tables_dev && tables_host && desc_dev && out && workspace && status_dev, IO_ERR_SHAPE,
                "jpeg_decode: null pointer");
-    JpegPlan plan;
+    JpegPlan& plan = *planp;
     const int rc = jpeg_check_desc(desc_host, n, &plan);
     if (rc != IO_OK) return rc;
     IO_REQUIRE((size_t)plan.n_sets * sizeof(io_jpeg_tables) <= tables_bytes, IO_ERR_SHAPE,
@@ -420,9 +570,37 @@ extern "C" int io_jpeg_decode_u8(const uint8_t* pool_dev, size_t pool_bytes, con
         IO_REQUIRE(d.out_off >= 0 && (size_t)d.out_off <= out_bytes && nb <= out_bytes - (size_t)d.out_off, IO_ERR_SHAPE,
                    "jpeg_decode: image %d output outside the output buffer", i);
     }
-    const size_t need = plan.off_bytes + plan.huff_bytes + plan.coef_bytes + plan.plane_bytes;
     IO_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)tables_dev & 15) == 0 && ((uintptr_t)desc_dev & 7) == 0,
                IO_ERR_SHAPE, "jpeg_decode: workspace and tables must be 16-byte aligned, descriptors 8-byte aligned");
+    return IO_OK;
+}
+
+// stages 2 and 3 behind either entropy stage
+void jpeg_launch_pixels(const JpegPlan& plan, const io_jpeg_tables* tables_dev, const io_jpeg_desc* desc_dev,
+                        const unsigned long long* off, const int16_t* coef, uint8_t* planes, uint8_t* out, int n, hipStream_t st) {
+    {
+        IoProfScope prof(IO_PROF_JPEG_IDCT, 0.0, (double)plan.coef_bytes + (double)plan.plane_bytes, st);
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3(io_cdiv(plan.total_blocks, kThreads)), dim3(kThreads), 0, st, tables_dev,
+                           desc_dev, off, coef, planes, n);
+    }
+    {
+        IoProfScope prof(IO_PROF_JPEG_COLOUR, 0.0, (double)plan.plane_bytes + plan.out_bytes, st);
+        hipLaunchKernelGGL(jpeg_colour_kernel, dim3(io_cdiv(plan.max_words, kChunkWords), n), dim3(kThreads), 0, st, desc_dev,
+                           off, planes, out);
+    }
+}
+
+}  // namespace
+
+extern "C" int io_jpeg_decode_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev,
+                                 const io_jpeg_tables* tables_host, size_t tables_bytes, const io_jpeg_desc* desc_dev,
+                                 const io_jpeg_desc* desc_host, int n, uint8_t* out, size_t out_bytes, void* workspace,
+                                 size_t workspace_bytes, int32_t* status_dev, hipStream_t st) {
+    JpegPlan plan;
+    const int rc = jpeg_check_call(pool_dev, pool_bytes, tables_dev, tables_host, tables_bytes, desc_dev, desc_host, n, out,
+                                   out_bytes, workspace, status_dev, &plan);
+    if (rc != IO_OK) return rc;
+    const size_t need = plan.off_bytes + plan.huff_bytes + plan.coef_bytes + plan.plane_bytes;
     IO_REQUIRE(workspace_bytes >= need, IO_ERR_WORKSPACE, "jpeg_decode: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     unsigned long long* off = reinterpret_cast<unsigned long long*>(ws);
@@ -440,15 +618,57 @@ extern "C" int io_jpeg_decode_u8(const uint8_t* pool_dev, size_t pool_bytes, con
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(io_cdiv(waves, kThreads / 64)), dim3(kThreads), 0, st, pool_dev, huff,
                            plan.n_sets, desc_dev, off, coef, status_dev, n, per_wave);
     }
-    {
-        IoProfScope prof(IO_PROF_JPEG_IDCT, 0.0, (double)plan.coef_bytes + (double)plan.plane_bytes, st);
-        hipLaunchKernelGGL(jpeg_idct_kernel, dim3(io_cdiv(plan.total_blocks, kThreads)), dim3(kThreads), 0, st, tables_dev,
-                           desc_dev, off, coef, planes, n);
-    }
-    {
-        IoProfScope prof(IO_PROF_JPEG_COLOUR, 0.0, (double)plan.plane_bytes + plan.out_bytes, st);
-        hipLaunchKernelGGL(jpeg_colour_kernel, dim3(io_cdiv(plan.max_words, kChunkWords), n), dim3(kThreads), 0, st, desc_dev,
-                           off, planes, out);
-    }
+    jpeg_launch_pixels(plan, tables_dev, desc_dev, off, coef, planes, out, n, st);
     return io_check_launch("jpeg_decode");
+}
+
+extern "C" size_t io_jpeg_par_workspace_bytes(const io_jpeg_desc* desc_host, int n, int subseq_bytes) {
+    JpegPlan plan;
+    JpegParPlan par;
+    if (jpeg_check_desc(desc_host, n, &plan) != IO_OK || jpeg_check_par(desc_host, n, subseq_bytes, &par) != IO_OK) return 0;
+    const size_t seq = plan.off_bytes + plan.huff_bytes + plan.coef_bytes + plan.plane_bytes;
+    return (seq + 15) / 16 * 16 + par.suboff_bytes + par.fallback_bytes + par.rec_bytes;
+}
+
+extern "C" int io_jpeg_decode_par_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev,
+                                     const io_jpeg_tables* tables_host, size_t tables_bytes, const io_jpeg_desc* desc_dev,
+                                     const io_jpeg_desc* desc_host, int n, uint8_t* out, size_t out_bytes, void* workspace,
+                                     size_t workspace_bytes, int32_t* status_dev, int subseq_bytes, int max_rounds,
+                                     int32_t* info_dev, hipStream_t st) {
+    JpegPlan plan;
+    JpegParPlan par;
+    int rc = jpeg_check_call(pool_dev, pool_bytes, tables_dev, tables_host, tables_bytes, desc_dev, desc_host, n, out, out_bytes,
+                             workspace, status_dev, &plan);
+    if (rc != IO_OK) return rc;
+    rc = jpeg_check_par(desc_host, n, subseq_bytes, &par);
+    if (rc != IO_OK) return rc;
+    IO_REQUIRE(max_rounds >= 1 && max_rounds <= JPEG_SYNC_MAX_ROUNDS, IO_ERR_SHAPE, "jpeg_decode_par: max_rounds=%d (1..%d)",
+               max_rounds, JPEG_SYNC_MAX_ROUNDS);
+    const size_t seq = (plan.off_bytes + plan.huff_bytes + plan.coef_bytes + plan.plane_bytes + 15) / 16 * 16;
+    const size_t need = seq + par.suboff_bytes + par.fallback_bytes + par.rec_bytes;
+    IO_REQUIRE(workspace_bytes >= need, IO_ERR_WORKSPACE, "jpeg_decode_par: workspace of %zu bytes, %zu needed", workspace_bytes,
+               need);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    unsigned long long* off = reinterpret_cast<unsigned long long*>(ws);
+    JpegHuff* huff = reinterpret_cast<JpegHuff*>(ws + plan.off_bytes);
+    int16_t* coef = reinterpret_cast<int16_t*>(ws + plan.off_bytes + plan.huff_bytes);
+    uint8_t* planes = ws + plan.off_bytes + plan.huff_bytes + plan.coef_bytes;
+    unsigned long long* suboff = reinterpret_cast<unsigned long long*>(ws + seq);
+    int32_t* fallback = reinterpret_cast<int32_t*>(ws + seq + par.suboff_bytes);
+    uint32_t* rec = reinterpret_cast<uint32_t*>(ws + seq + par.suboff_bytes + par.fallback_bytes);
+    const hipError_t e = hipMemsetAsync(coef, 0, plan.coef_bytes, st);
+    IO_REQUIRE(e == hipSuccess, IO_ERR_LAUNCH, "jpeg_decode_par: clearing the coefficients: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(jpeg_offsets_kernel, dim3(1), dim3(kThreads), 0, st, desc_dev, n, off);
+    hipLaunchKernelGGL(jpeg_sub_offsets_kernel, dim3(1), dim3(kThreads), 0, st, desc_dev, n, subseq_bytes, suboff);
+    hipLaunchKernelGGL(jpeg_tables_kernel, dim3(plan.n_sets), dim3(64), 0, st, tables_dev, huff);
+    {
+        // both launches in the class of the sequential stage: the fallback is part of what this stage costs
+        IoProfScope prof(IO_PROF_JPEG_ENTROPY, 0.0, (double)pool_bytes + (double)plan.coef_bytes + (double)par.rec_bytes, st);
+        hipLaunchKernelGGL(jpeg_sync_kernel, dim3(n), dim3(kThreads), 0, st, pool_dev, huff, desc_dev, off, suboff, rec, coef,
+                           status_dev, fallback, info_dev, subseq_bytes, max_rounds);
+        hipLaunchKernelGGL(jpeg_fallback_kernel, dim3(io_cdiv(n, kThreads / 64)), dim3(kThreads), 0, st, pool_dev, huff,
+                           plan.n_sets, desc_dev, off, coef, status_dev, fallback, n);
+    }
+    jpeg_launch_pixels(plan, tables_dev, desc_dev, off, coef, planes, out, n, st);
+    return io_check_launch("jpeg_decode_par");
 }

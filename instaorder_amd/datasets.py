@@ -266,7 +266,8 @@ class PairRenderer(object):
         for k, key in enumerate(jp_keys):
             jdesc[k].out_off = dec_at + dec[key]
         jws_at = (ws_at + ws_bytes + 15) // 16 * 16
-        jws_bytes = jpeg.workspace_bytes(jdesc) if jp_keys else 0
+        jent = jpeg.get_entropy()                                    # the stage jpeg.set_entropy names sizes the arena ...
+        jws_bytes = jpeg.workspace_bytes(jdesc, jent) if jp_keys else 0
         st_at = jws_at + jws_bytes
         for k, ((ii, i1, i2, box, interp, flip), (kimg, region, k1, k2)) in enumerate(zip(items, keys)):
             base = dec_at if region is dec else 0
@@ -297,12 +298,9 @@ class PairRenderer(object):
                                 descriptors=C.sizeof(rdesc) + sum(pbytes) + jdbytes + C.sizeof(desc), total=dec_at)
         base = dev.data_ptr()
         if jp_keys:
-            rc = _lib.lib().io_jpeg_decode_u8(C.c_void_p(base + jp_at), C.c_size_t(jpool.size), C.c_void_p(base + jt_at),
-                                              jtabs.ctypes.data_as(C.c_void_p), C.c_size_t(jtabs.size), C.c_void_p(base + jd_at),
-                                              C.cast(jdesc, C.c_void_p), len(jp_keys), C.c_void_p(base), C.c_size_t(nbytes),
-                                              C.c_void_p(base + jws_at), C.c_size_t(jws_bytes), C.c_void_p(base + st_at),
-                                              C.c_void_p(stream.cuda_stream))
-            _lib.check(rc, "io_jpeg_decode_u8")
+            # ... and is the entry point called: io_jpeg_decode_u8 or io_jpeg_decode_par_u8
+            jpeg.launch(jent, base + jp_at, jpool.size, base + jt_at, jtabs, base + jd_at, jdesc, base, nbytes, base + jws_at,
+                        jws_bytes, base + st_at, stream.cuda_stream)
             # the status words follow the batch to pinned memory; they are read when this staging slot comes round again
             words = torch.empty(len(jp_keys), dtype=torch.int32).pin_memory()
             words.copy_(dev[st_at:st_at + 4 * len(jp_keys)].view(torch.int32), non_blocking=True)

@@ -24,6 +24,10 @@ The rule (DESIGN.md "JPEG images") is the published baseline algorithm with libj
 ``JpegImage.to_host()`` is that rule in NumPy and the contract of the kernels.  Equality with libjpeg-turbo is claimed for
 streams whose dequantised coefficients fit int16 (its SIMD path holds them in 16 bits).  EXIF orientation is ignored, as
 ``convert('RGB')`` ignores it.
+
+Step 1 has two implementations on the device with the same result: one lane per image (``io_jpeg_decode_u8``, the default)
+and the lanes of a workgroup on the subsequences of one image (``io_jpeg_decode_par_u8``, csrc/jpeg_sync.h), chosen by
+``set_entropy``; ``JpegImage.parallel_plan`` is the rule of the latter in Python.
 """
 import ctypes as C
 import os
@@ -412,6 +416,267 @@ class JpegImage(object):
                 blk += 1
         return coef
 
+    # ---- the parallel entropy stage in Python (csrc/jpeg_sync.h) ---------------------------------------------------------
+    def _sync_context(self):
+        self._require()
+        _, huff = self._tables
+        hs, vs = self.luma_sampling
+        nc = len(self.components)
+        tabs = {}
+        for key, (cnt, sy) in huff.items():                  # 16-bit prefix -> length (0: no code) and symbol, as bytes
+            ln, sv = bytearray(1 << 16), bytearray(1 << 16)
+            code, k = 0, 0
+            for l in range(1, 17):
+                for _ in range(int(cnt[l - 1])):
+                    if code >= 1 << l:
+                        raise ValueError("JPEG %s: Huffman code lengths that form no prefix code" % self.name)
+                    lo, span = code << (16 - l), 1 << (16 - l)
+                    ln[lo:lo + span] = bytes([l]) * span
+                    sv[lo:lo + span] = bytes([int(sy[k])]) * span
+                    code += 1
+                    k += 1
+                code <<= 1
+            tabs[key] = (bytes(ln), bytes(sv))
+        sel = list(self.scan_tables) + [self.scan_tables[0]] * (3 - nc)
+        mw, mh = -(-self.W // (8 * hs)), -(-self.H // (8 * vs))
+        bpm = hs * vs + (2 if nc == 3 else 0)
+        return dict(p=self.entropy_bytes(), luma=hs * vs, bpm=bpm, ri=self.restart_interval, n_blocks=mw * mh * bpm,
+                    dc=[tabs[(0, td)] for td, ta in sel], ac=[tabs[(1, ta)] for td, ta in sel])
+
+    @staticmethod
+    def _sync_decode(cx, sub_end, max_passes, e_byte, e_brk, e_m, store=None):
+        """``jpeg_sync_decode`` of csrc/jpeg_sync.h, statement by statement.  store: None, or (coef int16 [n_blocks, 64],
+        first block, (p0, p1, p2)) for the write pass.  Returns (byte, brk, m, blocks, d0, d1, d2, markers, marker delta,
+        blocks before the first marker, blocks before the first violation or -1)."""
+        p, luma, bpm, ri, dct, act = cx["p"], cx["luma"], cx["bpm"], cx["ri"], cx["dc"], cx["ac"]
+        end = len(p)
+        n_blocks = cx["n_blocks"]
+        pos = min(max(e_byte, 0), end)
+        acc, n, stall = 0, 0, 0
+        units = []                                           # raw index of every byte unit taken since acc was last empty
+        r, k, m = (e_brk >> 8) & 255, (e_brk >> 16) & 255, e_m
+        if r >= bpm:
+            r = 0
+        if k > 63:
+            k = 0
+        blocks, nrst, rst_delta, rst_blocks, viol = 0, 0, 0, 0, -1
+        d = [0, 0, 0]
+        if store is not None:
+            coef, first_block, pr = store
+            pr = list(pr)
+        first = True
+        passes = 0
+        while True:
+            if not first:
+                if passes >= max_passes:
+                    if viol < 0:
+                        viol = blocks
+                    break
+                if store is not None and first_block + blocks >= n_blocks:
+                    break
+            while n < 32 and not stall:                      # jpeg_sync_refill
+                if pos >= end:
+                    stall = 1
+                elif p[pos] != 0xFF:
+                    acc = ((acc << 8) | p[pos]) & 0xFFFFFFFFFFFFFFFF
+                    units.append(pos)
+                    pos += 1
+                    n += 8
+                elif pos + 1 >= end:
+                    stall = 1
+                elif p[pos + 1] != 0:
+                    stall = 2
+                else:
+                    acc = ((acc << 8) | 0xFF) & 0xFFFFFFFFFFFFFFFF
+                    units.append(pos)
+                    pos += 2
+                    n += 8
+            if first:                                        # the bits of the entry's byte unit that are used already
+                first = False
+                bit = e_brk & 7
+                if bit and n >= 8:
+                    n -= bit
+                continue
+            nb = (n + 7) >> 3
+            if (units[len(units) - nb] if nb else pos) >= sub_end:
+                break
+            passes += 1
+            at_marker = False
+            if ri > 0 and r == 0 and k == 0 and m >= ri:
+                if n >= 8:
+                    if viol < 0:
+                        viol = blocks
+                    m = 0
+                elif stall == 1:
+                    break
+                else:
+                    at_marker = True
+            if not at_marker:
+                w = ((acc >> (n - 32)) if n >= 32 else (acc << (32 - n))) & 0xFFFFFFFF
+                comp = 0 if r < luma else 1 + (r - luma)
+                tab = dct[comp] if k == 0 else act[comp]
+                length = tab[0][w >> 16]
+                sym = tab[1][w >> 16] if length else -1
+                if sym < 0 and not (stall and n < 16):
+                    if viol < 0:
+                        viol = blocks
+                    n -= 1
+                    continue
+                size = sym if k == 0 else sym & 15
+                if k == 0 and sym > 15:
+                    if viol < 0:
+                        viol = blocks
+                    size = 0
+                if sym < 0 or length + size > n:
+                    if stall != 2:
+                        break
+                    if viol < 0:
+                        viol = blocks
+                    at_marker = True
+                else:
+                    val = 0
+                    if size:
+                        v = ((w << length) & 0xFFFFFFFF) >> (32 - size)
+                        val = v if v >= 1 << (size - 1) else v - (1 << size) + 1
+                    n -= length + size
+                    if k == 0:
+                        d[comp] += val
+                        if store is not None:
+                            pr[comp] += val
+                            if first_block + blocks < n_blocks:
+                                coef[first_block + blocks, 0] = np.int64(pr[comp]).astype(np.int16)
+                        k = 1
+                    else:
+                        run = sym >> 4
+                        if size == 0:
+                            if run == 15:
+                                k += 16
+                                if k > 64:
+                                    if viol < 0:
+                                        viol = blocks
+                                    k = 64
+                            else:
+                                k = 64
+                        else:
+                            k += run
+                            if k > 63:
+                                if viol < 0:
+                                    viol = blocks
+                                k = 64
+                            else:
+                                if store is not None and first_block + blocks < n_blocks:
+                                    coef[first_block + blocks, ZIGZAG[k]] = val
+                                k += 1
+                    if k >= 64:
+                        k = 0
+                        blocks += 1
+                        r += 1
+                        if r >= bpm:
+                            r = 0
+                            if ri > 0:
+                                m += 1
+                    continue
+            if stall != 2:
+                break
+            x = p[pos + 1]
+            if x == 0xFF:
+                pos += 1
+            elif x & 0xF8 == 0xD0:
+                dl = (x - nrst) & 7
+                if nrst == 0:
+                    rst_delta, rst_blocks = dl, blocks
+                elif dl != rst_delta and viol < 0:
+                    viol = blocks
+                nrst += 1
+                pos += 2
+                r = k = m = 0
+                d = [0, 0, 0]
+                if store is not None:
+                    pr = [0, 0, 0]
+            else:
+                if viol < 0:
+                    viol = blocks
+                break
+            n, stall = 0, 0
+            del units[:]
+        nb = (n + 7) >> 3
+        byte = units[len(units) - nb] if nb else pos
+        return (byte, ((8 - (n & 7)) & 7) | (r << 8) | (k << 16), m, blocks, d[0] & 0xFFFFFFFF, d[1] & 0xFFFFFFFF,
+                d[2] & 0xFFFFFFFF, nrst, rst_delta, rst_blocks, viol)
+
+    def parallel_plan(self, subseq_bytes, max_rounds, coefficients=False):
+        """What the parallel entropy stage (``io_jpeg_decode_par_u8``) does with this file, by the rule of csrc/jpeg_sync.h
+        in Python: dict(rounds, subsequences, live, decodes, fallback, blocks).  ``rounds | fallback`` is the info word of
+        the image: fallback is 0, 1 << 16 (no convergence within max_rounds) or 1 << 17 (converged, not clean); the
+        sequential stage decodes an image with a fallback.  live: subsequences up to the one that completes the last
+        block (0 with a fallback); decodes: subsequence decodes of all rounds; blocks: blocks per live subsequence.
+        With ``coefficients`` a clean image also gets "coefficients", the int16 [n_blocks, 64] of the write pass."""
+        if subseq_bytes % 8 or not 16 <= subseq_bytes <= 4096 or not 1 <= max_rounds <= 65535:
+            raise ValueError("parallel_plan: subseq_bytes %d (a multiple of 8 in 16..4096), max_rounds %d (1..65535)"
+                             % (subseq_bytes, max_rounds))
+        cx = self._sync_context()
+        p = cx["p"]
+        nbytes, n_blocks = len(p), cx["n_blocks"]
+        nsub = max(1, -(-nbytes // subseq_bytes))
+        ends = [min((i + 1) * subseq_bytes, nbytes) for i in range(nsub)]
+        entry = [(0, 0, 0)]
+        for i in range(1, nsub):                             # jpeg_sync_guess
+            g = min(i * subseq_bytes, nbytes)
+            if 1 <= g < nbytes and p[g - 1] == 0xFF and (p[g] == 0 or p[g] & 0xF8 == 0xD0):
+                g += 1
+            entry.append((g, 0, 0))
+        changed = [True] * nsub
+        exits = [None] * nsub
+        rounds, decodes, converged = 0, 0, False
+        passes = 8 * subseq_bytes + 32
+        while rounds < max_rounds and not converged:
+            for i in range(nsub):
+                if changed[i]:
+                    exits[i] = self._sync_decode(cx, ends[i], passes, *entry[i])
+                    decodes += 1
+            rounds += 1
+            converged = True
+            changed[0] = False
+            for i in range(1, nsub):
+                changed[i] = exits[i - 1][:3] != entry[i]
+                entry[i] = exits[i - 1][:3]
+                if changed[i]:
+                    converged = False
+        out = dict(rounds=rounds, subsequences=nsub, live=0, decodes=decodes, fallback=0, blocks=[])
+        if not converged:
+            out["fallback"] = 1 << 16
+            return out
+        first, markers, clean, full = 0, 0, True, False      # jpeg_sync_finish
+        pred = [0, 0, 0]
+        starts = []
+        for i in range(nsub):
+            byte, brk, m, blocks, d0, d1, d2, nrst, delta, rst_blocks, viol = exits[i]
+            starts.append((first, tuple(v & 0xFFFF for v in pred)))
+            if viol >= 0 and first + viol < n_blocks:
+                clean = False
+            if nrst > 0:
+                if first + rst_blocks < n_blocks and delta != markers & 7:
+                    clean = False
+                markers += nrst
+                pred = [0, 0, 0]
+            pred = [(a + (b & 0xFFFF)) & 0xFFFFFFFF for a, b in zip(pred, (d0, d1, d2))]
+            first += blocks
+            out["blocks"].append(blocks)
+            if first >= n_blocks:
+                full = True
+                break
+        if not (clean and full):
+            out["fallback"] = 1 << 17
+            out["blocks"] = []
+            return out
+        out["live"] = len(starts)
+        if coefficients:
+            coef = np.zeros((n_blocks, 64), np.int16)
+            for i, (fb, pr) in enumerate(starts):
+                self._sync_decode(cx, ends[i], passes, *entry[i], store=(coef, fb, pr))
+            out["coefficients"] = coef
+        return out
+
     def to_host(self):
         """uint8 [H, W, 3] by the rule of the module docstring, in NumPy: the contract of the kernels.  Slow."""
         coef = self.coefficients()
@@ -529,11 +794,70 @@ def descriptors(images, out_offs):
     return pool, tables, desc
 
 
-def workspace_bytes(desc):
-    b = int(_lib.lib().io_jpeg_workspace_bytes(C.cast(desc, C.c_void_p), len(desc)))
+# ---- which entropy stage the device decoder runs --------------------------------------------------------------------------
+_ENTROPY = dict(mode="sequential", subseq_bytes=256, max_rounds=64)
+
+
+def set_entropy(mode, subseq_bytes=256, max_rounds=64):
+    """The entropy stage of ``decode`` and of ``datasets.PairRenderer`` (so of the ``*Batches`` classes, the inference
+    drivers and ``evaluate``): "sequential", one lane per image (``io_jpeg_decode_u8``), or "parallel", the lanes of a
+    workgroup on the subsequences of one image (``io_jpeg_decode_par_u8``, csrc/jpeg_sync.h).  Pixels and status words do
+    not depend on it.  Module-wide; the default is "sequential", the environment variable IO_JPEG_ENTROPY=parallel selects
+    the other at import.  Any other non-empty value of that variable raises this function's ValueError when
+    ``instaorder_amd.jpeg`` is imported: a misspelt setting stops the program instead of running the other stage."""
+    if mode not in ("sequential", "parallel"):
+        raise ValueError("jpeg.set_entropy: mode %r ('sequential' or 'parallel')" % (mode,))
+    if subseq_bytes % 8 or not 16 <= subseq_bytes <= 4096 or not 1 <= max_rounds <= 65535:
+        raise ValueError("jpeg.set_entropy: subseq_bytes %d (a multiple of 8 in 16..4096), max_rounds %d (1..65535)"
+                         % (subseq_bytes, max_rounds))
+    _ENTROPY.update(mode=mode, subseq_bytes=int(subseq_bytes), max_rounds=int(max_rounds))
+
+
+def get_entropy(entropy=None):
+    """dict(mode, subseq_bytes, max_rounds): the module setting, with ``entropy`` ("sequential" / "parallel") in place of
+    its mode; such a dict is returned as it is"""
+    if isinstance(entropy, dict):
+        return dict(entropy)
+    e = dict(_ENTROPY)
+    if entropy is not None:
+        if entropy not in ("sequential", "parallel"):
+            raise ValueError("jpeg: entropy %r ('sequential' or 'parallel')" % (entropy,))
+        e["mode"] = entropy
+    return e
+
+
+if os.environ.get("IO_JPEG_ENTROPY", ""):
+    set_entropy(os.environ["IO_JPEG_ENTROPY"])
+
+
+def workspace_bytes(desc, entropy=None):
+    e = get_entropy(entropy)
+    if e["mode"] == "parallel":
+        fn = "io_jpeg_par_workspace_bytes"
+        b = int(_lib.lib().io_jpeg_par_workspace_bytes(C.cast(desc, C.c_void_p), len(desc), e["subseq_bytes"]))
+    else:
+        fn = "io_jpeg_workspace_bytes"
+        b = int(_lib.lib().io_jpeg_workspace_bytes(C.cast(desc, C.c_void_p), len(desc)))
     if b == 0:
-        raise RuntimeError("instaorder_hip io_jpeg_workspace_bytes refused the descriptors: %s" % _lib.last_error())
+        raise RuntimeError("instaorder_hip %s refused the descriptors: %s" % (fn, _lib.last_error()))
     return b
+
+
+def launch(entropy, pool, pool_bytes, tables_dev, tables, desc_dev, desc, out, out_bytes, ws, ws_bytes, status, stream,
+           info=None):
+    """one ``io_jpeg_decode_u8`` / ``io_jpeg_decode_par_u8`` call, as ``entropy`` (a ``get_entropy`` dict) says.  Device
+    addresses as ints; ``tables``: the host uint8 array, ``desc``: the host JpegDesc array, ``info``: n int32 or None."""
+    head = (C.c_void_p(pool), C.c_size_t(pool_bytes), C.c_void_p(tables_dev), tables.ctypes.data_as(C.c_void_p),
+            C.c_size_t(tables.size), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p), len(desc), C.c_void_p(out),
+            C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status))
+    if entropy["mode"] == "parallel":
+        fn = "io_jpeg_decode_par_u8"
+        rc = _lib.lib().io_jpeg_decode_par_u8(*(head + (entropy["subseq_bytes"], entropy["max_rounds"],
+                                                        C.c_void_p(info) if info else None, C.c_void_p(stream))))
+    else:
+        fn = "io_jpeg_decode_u8"
+        rc = _lib.lib().io_jpeg_decode_u8(*(head + (C.c_void_p(stream),)))
+    _lib.check(rc, fn)
 
 
 def raise_for_status(status, images):
@@ -544,16 +868,19 @@ def raise_for_status(status, images):
                                                                for nm, s in bad))
 
 
-def decode(images, device, out=None):
+def decode(images, device, out=None, entropy=None, info=False):
     """list of supported ``JpegImage`` -> list of uint8 [H, W, 3] device tensors through one ``io_jpeg_decode_u8`` call on
     the current stream (views of ``out``, a contiguous uint8 device tensor of at least the summed sizes, when given).
-    Waits for the status words and raises RuntimeError naming the images that did not decode."""
+    Waits for the status words and raises RuntimeError naming the images that did not decode.  ``entropy``: "sequential"
+    or "parallel" instead of the ``set_entropy`` mode.  With ``info`` the result is (tensors, int32 array): the info word
+    of every image (``JpegImage.parallel_plan``; zeros from the sequential stage)."""
     import torch
     _lib.require_gpu()
     device = torch.device(device)
     images = list(images)
+    setting = get_entropy(entropy)
     if not images:
-        return []
+        return ([], np.zeros(0, np.int32)) if info else []
     for im in images:
         if not is_jpeg(im):
             raise TypeError("jpeg.decode takes JpegImage objects (got %s)" % type(im).__name__)
@@ -578,17 +905,16 @@ def decode(images, device, out=None):
     for a, b in zip(at, blobs):
         host[a:a + b.size] = b
     dev = torch.from_numpy(host).to(out.device)
-    ws = torch.empty(workspace_bytes(desc), dtype=torch.uint8, device=out.device)
+    ws = torch.empty(workspace_bytes(desc, setting), dtype=torch.uint8, device=out.device)
     status = torch.empty(len(images), dtype=torch.int32, device=out.device)
+    words = torch.zeros(len(images), dtype=torch.int32, device=out.device)
     base = dev.data_ptr()
-    rc = _lib.lib().io_jpeg_decode_u8(
-        C.c_void_p(base + at[2]), C.c_size_t(pool.size), C.c_void_p(base + at[0]), tables.ctypes.data_as(C.c_void_p),
-        C.c_size_t(tables.size), C.c_void_p(base + at[1]), C.cast(desc, C.c_void_p), len(images), C.c_void_p(out.data_ptr()),
-        C.c_size_t(out.numel()), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), C.c_void_p(status.data_ptr()),
-        C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream))
-    _lib.check(rc, "io_jpeg_decode_u8")
+    launch(setting, base + at[2], pool.size, base + at[0], tables, base + at[1], desc, out.data_ptr(), out.numel(),
+           ws.data_ptr(), ws.numel(), status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream,
+           info=words.data_ptr() if info else None)
     raise_for_status(status.cpu().numpy(), images)
-    return [out[o:o + s].view(im.H, im.W, 3) for o, s, im in zip(offs, sizes, images)]
+    res = [out[o:o + s].view(im.H, im.W, 3) for o, s, im in zip(offs, sizes, images)]
+    return (res, words.cpu().numpy()) if info else res
 
 
 def _pil_rgb(path):
