@@ -277,6 +277,23 @@ int io_net_backward_num_stages(const io_net* net);
 int io_net_backward_stages(io_net* net, const float* params, float* grads, const void* x8, const float* dlogits, int N,
                            int S, int G, void* workspace, size_t workspace_bytes, int stage_lo, int stage_hi,
                            hipStream_t stream);
+/* What a training step of that shape runs, per Bottleneck block: the executor's route table (read-only: launches nothing,
+ * needs no device).  The environment the routes may depend on comes in as arguments -- p256_mode / xop: the values of
+ * io_set_bf16_p256 / io_set_bf16_p256_xop, ncu: the CU count of the device -- so any combination can be asked about.
+ * Writes one word per block to out[0 .. blocks) and returns the number of blocks (16), or a negative IO_ERR_* code
+ * (bad shape; G that no workspace layout serves; max_blocks too small).  Bits of a word:
+ *    0-1  who builds the block output relu(bn3(y3) + identity): 0 a BatchNorm pass of its own, 1 the next block's conv1 on
+ *         conv_nt_kernel, 2 the next block's conv1 on the 256-row bf16 kernel
+ *    2, 3 the BatchNorm groups of the block input / output fill whole 128-row tiles
+ *    4, 5 conv2 / conv3 read relu(bn(y)) through the input transform (the activation is not stored)
+ *    6    the forward wrote the one-bit ReLU mask of the block output
+ *    7    bn3's backward leaves its apply pass to conv3's data gradient;  8  ... on the 256-row bf16 kernel
+ *    9    bn1's backward leaves its apply pass to conv1's data gradient (stride-1 conv2);  10  ... (strided conv2)
+ *    11   conv1's data gradient carries the reductions of the previous block's bn3
+ *    12   bn3's reductions were produced by the next block's conv1 data gradient
+ *    13, 14, 15  the workspace holds relu(bn1(y1)) / relu(bn2(y2)) / the one-bit mask of the output
+ *    16-17  backward stage of the block (io_net_backward_stages) */
+int io_net_step_routes(const io_net* net, int N, int S, int G, int p256_mode, int xop, int ncu, int32_t* out, int max_blocks);
 int io_net_backward(io_net* net, const float* params, float* grads, const void* x8, const float* dlogits, int N,
                     int S, int G, void* workspace, size_t workspace_bytes, hipStream_t stream);
 

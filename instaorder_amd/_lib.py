@@ -166,6 +166,8 @@ SIGNATURES = {
     "io_net_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "io_net_backward_num_stages": (_I, [_P]),
     "io_net_backward_stages": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _I, _I, _P]),
+    # net, N, S, G, p256_mode, xop, ncu, out (host int32[max_blocks]), max_blocks
+    "io_net_step_routes": (_I, [_P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _I]),
     "io_net_set_dtype": (_I, [_P, _I]),
     "io_net_get_dtype": (_I, [_P]),
     "io_pack_planes_nhwc8_dt": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),

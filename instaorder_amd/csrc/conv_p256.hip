@@ -523,8 +523,6 @@ __global__ __launch_bounds__(512, 2) void conv_p256_kernel(IoConvGeom g, P256Arg
     }
 }
 
-int p256_ncu() { return io_device_cu_count(); }
-
 std::atomic<int> g_p256{-1};          // -1: not read from the environment yet
 int p256_enabled() {
     int on = g_p256.load(std::memory_order_relaxed);
@@ -539,10 +537,9 @@ int p256_enabled() {
 // One 512-thread block per CU walks the tiles: with few tiles, or a last round that leaves most CUs idle, the 128-row
 // kernel (four times the blocks, three per CU) fills the chip better -- measured on the MiDaS step at 16 pairs (24 x 24
 // and 12 x 12 maps: 9..144 row tiles), where taking every eligible launch cost 2.8 %.
-bool p256_rounds_ok(long tiles) {
-    const int ncu = p256_ncu();
-    const long rounds = (tiles + ncu - 1) / ncu;
-    return p256_enabled() == 3 || tiles * 10 >= rounds * ncu * 8;          // at least 80 % of the rounds' slots used
+bool p256_rounds_ok(long tiles, const IoRouteEnv& env) {
+    const long rounds = (tiles + env.ncu - 1) / env.ncu;
+    return env.p256_mode == 3 || tiles * 10 >= rounds * env.ncu * 8;          // at least 80 % of the rounds' slots used
 }
 
 // IO_P256_XOP=0 / io_set_bf16_p256_xop(0): the operand forms stay on conv_nt_kernel / separate BatchNorm passes (A/B runs)
@@ -557,7 +554,50 @@ int xop_enabled() {
     return on;
 }
 
+// Does conv_p256_kernel take this launch, and as which instantiation?  The ONE acceptance test of the kernel: the launcher
+// below launches what it says, and io_conv_p256_takes_xop asks it about the launches the network executor plans.  A pure
+// function of its arguments: the switches and the CU count come in through env.
+struct P256Decision {
+    bool take;          // false: not this kernel's shape / form (every other field is then meaningless)
+    int bn, epi;        // output-channel tile width (256 | 128), epilogue (EPI_*)
+    bool lin, xop;      // dense 1x1 (linear A addressing); operand form (IoBwStats::xb_a) as an in-LDS transform
+    int xmode;          // xop: 1 = backward form, 2 = forward residual form, 3 = ... with a downsample branch (xb_res == 2)
+    long tiles;
+};
+P256Decision p256_decide(const IoConvGeom& g, bool add, bool mask, bool st_mean, const IoBwStats* bw, const IoRouteEnv& env) {
+    P256Decision d{};
+    if (!env.p256_mode) return d;
+    const long M = (long)g.N * g.Ho * g.Wo;
+    const bool dense_out = g.os == 1 && g.Ho == g.outH && g.Wo == g.outW;
+    if (g.gw || g.cr || !dense_out || M % 256 != 0 || g.Ci % 64 != 0 || g.Co % 128 != 0 || g.Th * g.Tw < 1) return d;
+    if (bw && (bw->in_scale || bw->a_out || bw->wino_u)) return d;
+    d.lin = g.Th * g.Tw == 1 && g.is == 1 && g.dh0 == 0 && g.dw0 == 0 && g.Hi == g.Ho && g.Wi == g.Wo;
+    // the operand forms (IoBwStats::xb_a) as an in-LDS transform: dense 1x1 launches, groups of whole 256-row tiles
+    d.xop = bw && bw->xb_a;
+    if (d.xop && (!d.lin || !env.xop || g.Ci > kXopMaxCi || !bw->xb_b || !bw->xb_c || !bw->xb_y || bw->xb_Mg <= 0 || bw->xb_Mg % 256 != 0 ||
+                  M % bw->xb_Mg != 0 || add || mask || bw->maskbits || bw->bias))
+        return d;
+    if (st_mean && (add || mask || (bw && (bw->y || bw->bias)))) return d;
+    if (bw && bw->y && (bw->Mg % 256 != 0 || bw->bias)) return d;
+    if (bw && bw->y && bw->mscale && (add || mask || bw->maskbits)) return d;         // (the executor never combines them)
+    // 32-bit offsets inside a tile's reach: 256 rows of the output, the samples a tile touches of the input
+    const double span = 256.0 / ((double)g.Ho * g.Wo) + 2.0;
+    if (span * 2.0 * g.Hi * g.Wi * g.Ci >= 4.0e9 || 256.0 * g.Co * 2.0 >= 4.0e9) return d;
+    if (g.Hi >= 32768 || g.Wi >= 32768) return d;
+    // where the 256-wide tile pays (tools/bf16_dma_probe.hip): N >= 256; 128-wide tiles for N = 128 (mod 256)
+    d.bn = g.Co % 256 == 0 ? 256 : 128;
+    d.epi = st_mean ? EPI_STATS : ((bw && bw->y) ? (bw->mscale ? EPI_BWE : EPI_BWE_READ) : EPI_PLAIN);
+    d.xmode = !d.xop ? 0 : (bw->xb_res == 2 ? 3 : (bw->xb_res ? 2 : 1));
+    if (d.xop && (d.epi == EPI_BWE_READ || (d.epi == EPI_BWE && d.xmode == 2))) return d;   // (not instantiated: the executor has no such launch)
+    d.tiles = (M / 256) * (g.Co / d.bn);
+    if (d.tiles >= (1L << 31) || !p256_rounds_ok(d.tiles, env)) return d;
+    d.take = true;
+    return d;
+}
+
 }  // namespace
+
+IoRouteEnv io_route_env_now() { return IoRouteEnv{p256_enabled(), xop_enabled(), io_device_cu_count()}; }
 
 extern "C" int io_get_bf16_p256_xop(void) { return xop_enabled(); }
 extern "C" int io_set_bf16_p256_xop(int on) {
@@ -565,13 +605,14 @@ extern "C" int io_set_bf16_p256_xop(int on) {
     g_xop.store(on ? 1 : 0, std::memory_order_relaxed);
     return prev;
 }
-// Would io_launch_conv_p256 take a dense 1x1 launch [M x Ci] -> [M x Co] WITH an operand form (executor: is the BatchNorm
-// pass worth leaving to the consumer's operand load in bf16)?  Same tests as the launcher, shape part only.
-bool io_conv_p256_takes_xop(long M, int Ci, int Co, int Mg) {
-    if (!p256_enabled() || !xop_enabled()) return false;
-    if (M % 256 != 0 || Ci % 64 != 0 || Ci > kXopMaxCi || Co % 128 != 0 || Mg <= 0 || Mg % 256 != 0 || M % Mg != 0) return false;
-    if (256.0 * Ci * 2.0 >= 4.0e9 || 256.0 * Co * 2.0 >= 4.0e9) return false;
-    return p256_rounds_ok(M / 256 * (Co / (Co % 256 == 0 ? 256 : 128)));
+// Would io_launch_conv_p256 take the dense 1x1 launch [N x H x W x Ci] -> [.. x Co] WITH an operand form over groups of Mg
+// rows (executor: is the BatchNorm pass worth leaving to the consumer's operand load in bf16)?  The launcher's own answer
+// (p256_decide) for that geometry and a representative operand-form IoBwStats.
+bool io_conv_p256_takes_xop(const IoRouteEnv& env, int N, int H, int W, int Ci, int Co, int Mg) {
+    IoBwStats bw{};
+    bw.xb_y = bw.xb_a = bw.xb_b = bw.xb_c = reinterpret_cast<const float*>(&bw);      // (tested for presence only)
+    bw.xb_Mg = Mg;
+    return p256_decide(io_geom_fwd(N, H, W, Ci, Co, 1, 1, 1, 0), false, false, false, &bw, env).take;
 }
 
 extern "C" int io_get_bf16_p256(void) { return p256_enabled(); }
@@ -583,31 +624,16 @@ extern "C" int io_set_bf16_p256(int on) {
 int io_bf16_persist_mode() { return p256_enabled(); }
 
 // Returns IO_OK when the launch was taken, 1 when the shape / form is not this kernel's (the caller falls through to
-// conv_nt_kernel), < 0 on a launch error.
+// conv_nt_kernel), < 0 on a launch error.  (A public single-op entry has no executor context: the switches are read here.)
 int io_launch_conv_p256(const IoConvGeom& g, const void* in, const void* wgt, void* out, const void* add, const void* mask,
                         hipStream_t st, float* st_mean, float* st_m2, const IoBwStats* bw, size_t in_bytes,
                         unsigned w_bytes, size_t out_bytes) {
-    if (!p256_enabled()) return 1;
+    const IoRouteEnv env = io_route_env_now();
+    const P256Decision d = p256_decide(g, add != nullptr, mask != nullptr, st_mean != nullptr, bw, env);
+    if (!d.take) return 1;
     const long M = (long)g.N * g.Ho * g.Wo;
-    const bool dense_out = g.os == 1 && g.Ho == g.outH && g.Wo == g.outW;
-    if (g.gw || g.cr || !dense_out || M % 256 != 0 || g.Ci % 64 != 0 || g.Co % 128 != 0 || g.Th * g.Tw < 1) return 1;
-    if (bw && (bw->in_scale || bw->a_out || bw->wino_u)) return 1;
-    const bool lin = g.Th * g.Tw == 1 && g.is == 1 && g.dh0 == 0 && g.dw0 == 0 && g.Hi == g.Ho && g.Wi == g.Wo;
-    // the operand forms (IoBwStats::xb_a) as an in-LDS transform: dense 1x1 launches, groups of whole 256-row tiles
-    const bool xop = bw && bw->xb_a;
-    if (xop && (!lin || !xop_enabled() || g.Ci > kXopMaxCi || !bw->xb_b || !bw->xb_c || !bw->xb_y || bw->xb_Mg <= 0 || bw->xb_Mg % 256 != 0 ||
-                M % bw->xb_Mg != 0 || add || mask || bw->maskbits || bw->bias))
-        return 1;
-    if (st_mean && (add || mask || (bw && (bw->y || bw->bias)))) return 1;
-    if (bw && bw->y && (bw->Mg % 256 != 0 || bw->bias)) return 1;
-    if (bw && bw->y && bw->mscale && (add || mask || bw->maskbits)) return 1;         // (the executor never combines them)
-    // 32-bit offsets inside a tile's reach: 256 rows of the output, the samples a tile touches of the input
-    const double span = 256.0 / ((double)g.Ho * g.Wo) + 2.0;
-    if (span * 2.0 * g.Hi * g.Wi * g.Ci >= 4.0e9 || 256.0 * g.Co * 2.0 >= 4.0e9) return 1;
-    if (g.Hi >= 32768 || g.Wi >= 32768) return 1;
-    // where the 256-wide tile pays (tools/bf16_dma_probe.hip): N >= 256; 128-wide tiles for N = 128 (mod 256)
-    const int bn = g.Co % 256 == 0 ? 256 : 128;
-    const int epi = st_mean ? EPI_STATS : ((bw && bw->y) ? (bw->mscale ? EPI_BWE : EPI_BWE_READ) : EPI_PLAIN);
+    const bool lin = d.lin, xop = d.xop;
+    const int bn = d.bn, epi = d.epi;
     P256Args a;
     memset(&a, 0, sizeof(a));
     a.in = (const bf16_t*)in;
@@ -628,16 +654,12 @@ int io_launch_conv_p256(const IoConvGeom& g, const void* in, const void* wgt, vo
         a.xc = bw->xb_c;
         a.xout = (bf16_t*)bw->xb_out;
         a.xbits = (uint8_t*)bw->xb_bits;
-        a.xmode = bw->xb_res == 2 ? 3 : (bw->xb_res ? 2 : 1);
+        a.xmode = d.xmode;
         a.xMg = bw->xb_Mg;
     }
     a.ntn = g.Co / bn;
-    const long tiles = (M / 256) * a.ntn;
-    if (tiles >= (1L << 31)) return 1;
-    a.ntiles = (int)tiles;
-    const int ncu = p256_ncu();
-    if (!p256_rounds_ok(tiles)) return 1;
-    const int grid = a.ntiles < ncu ? a.ntiles : ncu;
+    a.ntiles = (int)d.tiles;
+    const int grid = a.ntiles < env.ncu ? a.ntiles : env.ncu;
     const double kred = (double)g.Th * g.Tw * g.Ci;
     IoProfScope prof(bn == 256 ? IO_PROF_CONV_NT128 : IO_PROF_CONV_NT64, 2.0 * (double)M * g.Co * kred,
                      2.0 * M * g.Co * (1.0 + (add ? 1.0 : 0.0) + (mask ? 1.0 : 0.0) + ((bw && bw->y) ? 1.0 : 0.0)) +
@@ -670,7 +692,6 @@ int io_launch_conv_p256(const IoConvGeom& g, const void* in, const void* wgt, vo
         else if (epi == EPI_BWE) IO_P256_LAUNCH(BN_, EPI_BWE, false, 1);   \
         else IO_P256_LAUNCH(BN_, EPI_PLAIN, false, 1);                     \
     } while (0)
-    if (xop && (epi == EPI_BWE_READ || (epi == EPI_BWE && a.xmode == 2))) return 1;   // (not instantiated: the executor has no such launch)
     if (xop) {
         if (bn == 256) IO_P256_XOP(256);
         else IO_P256_XOP(128);

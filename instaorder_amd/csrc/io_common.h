@@ -193,8 +193,19 @@ int io_launch_conv_nt(const IoConvGeom& g, const void* in, const void* wgt, void
                       const void* mask, int stem, hipStream_t st, float* st_mean = nullptr,
                       float* st_m2 = nullptr, const IoBwStats* bw = nullptr, int dt_in = IO_F32,
                       int dt_out = IO_F32);
-// conv_p256.hip: would the 256-row bf16 kernel take a dense 1x1 launch [M x Ci] -> [M x Co] with an operand form (xb_a)?
-bool io_conv_p256_takes_xop(long M, int Ci, int Co, int Mg);
+// What a route decision may depend on besides the network, the shape and the dtype: the two process-wide bf16 switches
+// (io_set_bf16_p256, io_set_bf16_p256_xop) and the CU count of the current device.  io_route_env_now() reads them; the
+// network executor does so ONCE per entry point and decides every route of that call from the copy.
+// No decision that depends on these crosses from io_net_forward to io_net_backward*: what the backward must know about the
+// forward is what was STORED (a1 / a2, the one-bit mask, the block output), and that follows from dtype, planes, the shape
+// and compile-time constants alone (net.hip BlockRoute) -- so the two calls need no shared snapshot of the switches.
+struct IoRouteEnv {
+    int p256_mode, xop, ncu;
+};
+IoRouteEnv io_route_env_now();
+// conv_p256.hip: would the 256-row bf16 kernel take the dense 1x1 launch [N x H x W x Ci] -> [.. x Co] with an operand form
+// (xb_a) over BatchNorm groups of Mg rows?  The launcher's own acceptance test, under env.
+bool io_conv_p256_takes_xop(const IoRouteEnv& env, int N, int H, int W, int Ci, int Co, int Mg);
 // conv_p256.hip: IO_OK = launched, 1 = not this kernel's shape / form (fall through), < 0 = error
 int io_launch_conv_p256(const IoConvGeom& g, const void* in, const void* wgt, void* out, const void* add, const void* mask,
                         hipStream_t st, float* st_mean, float* st_m2, const IoBwStats* bw, size_t in_bytes,

@@ -101,7 +101,7 @@ BnL add_bn(io_net* net, const char* name, int C) {
 // ---- workspace plan ---------------------------------------------------------------------------
 constexpr size_t kNoBuf = ~(size_t)0;
 struct BlockBufs {
-    size_t y1, a1, y2, a2, y3, yd, out;   // byte offsets (a1 / a2 = kNoBuf: never materialised, see fuse_in)
+    size_t y1, a1, y2, a2, y3, yd, out;   // byte offsets (a1 / a2 = kNoBuf: never materialised, see reads_through_bn)
     size_t bits;                          // training: [out > 0] as one bit per element (IoBwStats::maskbits), kNoBuf: none
 };
 struct Plan {
@@ -112,7 +112,7 @@ struct Plan {
     size_t tile_mean, tile_m2;   // fused-statistics partials written by the conv epilogue (training)
     size_t gbuf[5];      // gradient scratch (training only)
     size_t aside;        // fp32 training: relu(bn(y)) of ONE layer at a time, rebuilt by the data-gradient epilogue for
-                         // the filter gradient that wants it (see fuse_in)
+                         // the filter gradient that wants it (see BlockRoute::f2)
     size_t wt, wg_partial, wg_partial_bytes;
     size_t wop;          // bf16 mode: operand copy of the whole flat parameter buffer (same element offsets)
     size_t stem_wp, stem_dwp;   // fp32: exact-K stem filter / filter gradient, [64][io_stem_kp]
@@ -130,6 +130,26 @@ struct Arena {
         return o;
     }
 };
+
+// ---- the predicates the workspace layout (make_plan) and the route table (plan_routes) share ---------------------------
+// do the BatchNorm groups of a tensor with M rows fill whole 128-row tiles (the granule of every fused statistic)?
+bool whole_tiles(long M, int G) { return M % G == 0 && (M / G) % kIoStatTileRows == 0; }
+
+// fp32: relu(bn1(y1)) / relu(bn2(y2)) are applied to the operand of conv2 / conv3 (and of their filter
+// gradients) as it is staged; the tensors exist only where that cannot run -- bf16 mode (the VALU work
+// does not hide under the 16x faster MFMA: measured) and shapes whose BatchNorm groups do not
+// fill whole 128-row tiles for some group count G | 8.
+// With G the call's group count this is BlockRoute::f3; with kMaxGroups it is "a2 is not in the plan" (act_never_stored):
+// the plan holds for every G | 8, a route for one G, and f3 may be true only where the plan left the tensor out.
+bool reads_through_bn(int dtype, long Mout, int G) { return dtype == IO_F32 && whole_tiles(Mout, G); }
+bool act_never_stored(int dtype, long Mout) { return reads_through_bn(dtype, Mout, kMaxGroups); }
+
+// bf16: the ReLU mask of the block output as one bit per element, for the data gradient that completes d(out) on
+// the 256-row kernel (conv_p256.hip): 1/16 of the tensor it would otherwise read.  Written by the BatchNorm pass
+// that builds the output; outputs built inside the next conv1 on conv_nt_kernel (out_route 1) have none.  fp32 never: measured round 5 --
+// packing the bits in conv_nt_kernel's operand staging and reading them in its column-layout epilogue cost the
+// fp32 step 3 % (59.7 -> 64.6 ms in the 128-wide class) for 4 of 136 bytes per element saved.
+bool bits_allocated(int dtype, long Mout) { return dtype == IO_BF16 && Mout % 256 == 0; }
 
 // SW: input width when it differs from the height S (eval only: the 'orig' inference mode feeds whole images at their
 // own aspect ratio); 0 = square
@@ -173,12 +193,8 @@ Plan make_plan(const io_net* net, int N, int S, bool training, int SW = 0) {
             const Block& b = net->blocks[i];
             const int Ho = H / b.stride;
             BlockBufs& bb = p.blk[i];
-            // fp32: relu(bn1(y1)) / relu(bn2(y2)) are applied to the operand of conv2 / conv3 (and of their filter
-            // gradients) as it is staged; the tensors exist only where that cannot run -- bf16 mode (the VALU work
-            // does not hide under the 16x faster MFMA: measured) and shapes whose BatchNorm groups do not
-            // fill whole 128-row tiles for some group count G | 8
             const long Mo = (long)N * Ho * Ho;
-            const bool never = net->dtype == IO_F32 && Mo % kMaxGroups == 0 && (Mo / kMaxGroups) % kIoStatTileRows == 0;
+            const bool never = act_never_stored(net->dtype, Mo);
             bb.y1 = a.take((size_t)N * H * H * b.planes * e);
             bb.a1 = (never && b.stride == 1) ? kNoBuf : a.take((size_t)N * H * H * b.planes * e);
             bb.y2 = a.take((size_t)N * Ho * Ho * b.planes * e);
@@ -186,12 +202,7 @@ Plan make_plan(const io_net* net, int N, int S, bool training, int SW = 0) {
             bb.y3 = a.take((size_t)N * Ho * Ho * b.planes * 4 * e);
             bb.yd = b.down ? a.take((size_t)N * Ho * Ho * b.planes * 4 * e) : 0;
             bb.out = a.take((size_t)N * Ho * Ho * b.planes * 4 * e);
-            // bf16: the ReLU mask of the block output as one bit per element, for the data gradient that completes d(out) on
-            // the 256-row kernel (conv_p256.hip): 1/16 of the tensor it would otherwise read.  Written by the BatchNorm pass
-            // that builds the output; outputs built inside the next conv1 on conv_nt_kernel (xr_route 1) have none.  fp32 never: measured round 5 --
-            // packing the bits in conv_nt_kernel's operand staging and reading them in its column-layout epilogue cost the
-            // fp32 step 3 % (59.7 -> 64.6 ms in the 128-wide class) for 4 of 136 bytes per element saved.
-            bb.bits = (net->dtype == IO_BF16 && Mo % 256 == 0) ? a.take((size_t)Mo * b.planes * 4 / 8) : kNoBuf;
+            bb.bits = bits_allocated(net->dtype, Mo) ? a.take((size_t)Mo * b.planes * 4 / 8) : kNoBuf;
             H = Ho;
         }
         for (int i = 0; i < 5; ++i) p.gbuf[i] = a.take(maxact);
@@ -245,6 +256,116 @@ Plan make_plan(const io_net* net, int N, int S, bool training, int SW = 0) {
     return p;
 }
 
+// ---- route table: what the training step runs for each Bottleneck block ---------------------------------------------
+#ifndef IO_XB_BF16_MAXP
+#define IO_XB_BF16_MAXP 64
+#endif
+#ifndef IO_XB_BF16_L1
+#define IO_XB_BF16_L1 1   // bf16: the operand forms on the layer-1 (64-plane) blocks only
+#endif
+constexpr int kBwdStages = 4;
+using RouteEnv = IoRouteEnv;      // (io_common.h: the switches and the CU count, and why no decision made from them outlives a call)
+
+// One row per block, filled by plan_routes and only READ by run_forward / run_backward.  Which decisions cross from
+// io_net_forward to io_net_backward*: the storage ones (a1_stored, a2_stored, bits_alloc -- make_plan's own predicates -- and
+// bits_written, i.e. out_route != 1), none of which depends on RouteEnv; out_route 0 against 2, x3p and everything else
+// that does depend on it is used inside one call only.
+struct BlockRoute {
+    int H, Ho, Min, Mout;         // input / output resolution, rows of the block input / output
+    int stage;                    // backward stage: the blocks of one resolution, last resolution first
+    bool tiles_in, tiles_out;     // whole_tiles(Min | Mout, G)
+    bool a1_stored, a2_stored, bits_alloc;     // the plan has relu(bn1(y1)) / relu(bn2(y2)) / the one-bit mask of the output
+    // Does conv2 / conv3 read its input through the producer's BatchNorm + ReLU instead of
+    // from a stored activation?  fp32 with whole 128-row tiles per BatchNorm group; the forward then never writes
+    // relu(bn(y)), and the backward gets it back for the one filter gradient that needs it as a side output of the
+    // data-gradient launch that recomputes the ReLU mask from y anyway (IoBwStats::a_out).  (Transforming the operand of the
+    // filter-gradient kernel the same way was measured: +20..35 % on the 128 x 128 tiles, which have no registers to spare.)
+    // (the strided conv2 of a stage's first block keeps a1: its data gradient runs as parity classes and cannot rebuild it)
+    bool f2, f3;
+    // Is the output of the block -- out = relu(bn3(y3) + identity) -- built by the NEXT block's conv1 while it
+    // stages its operand (conv_fwd's xr) instead of by a pass of its own?  fp32 (there the transform hides under the MFMAs),
+    // whole 128-row tiles per group; the caller also needs an identity that is a plain tensor (no downsample branch) and a
+    // next block.  Like the backward form: a 12 B / element pass becomes 8 B / element inside a GEMM.
+    // Who builds it?  0: a BatchNorm pass of its own (bn_act); 1: the NEXT
+    // block's conv1 on conv_nt_kernel's staging registers (fp32; bf16 only on the 64-plane blocks of layer 1 -- the form is VALU-bound
+    // next to bf16 MFMAs, but those launches are so HBM-bound that dropping the pass still wins, as for the backward form, x3);
+    // 2 (bf16, round 6): the next block's conv1 on the 256-row kernel, the transform applied IN LDS to every A k-tile after its DMA
+    // has landed (conv_p256.hip XOP) -- that launch also writes the one-bit mask of the output.
+    int out_route;
+    // ... and whether the forward wrote the one-bit mask: block outputs built by the next block's conv1 on conv_nt_kernel
+    // have no launch that does
+    bool bits_written;
+    // Does a BatchNorm backward leave its apply pass to the data-gradient kernel that consumes dy
+    // (IoBwStats::xb_a: dy = a * dz + b * y + c evaluated on the staged operand, written out once for the filter gradient)?
+    // fp32 only: there the transform hides under the MFMAs (as the forward one does); whole 128-row tiles per group.
+    // Applied: bn3 -> conv3's, bn1 -> conv1's (also of the three blocks whose conv2 is strided), the downsample BatchNorm's -> the
+    // downsample convolution's data gradient, the stem's bn1 in the staging of the stem's filter gradient (stem.hip).  NOT bn2 ->
+    // conv2's 3x3 data gradient (measured: a loss, below).
+    // Where it holds, the apply pass of a BatchNorm backward (read dz, read y, write dy) does not exist: the reductions
+    // become three coefficient tables and the data-gradient launch that consumes dy evaluates it on its operand --
+    // dz and y are loaded side by side, dy = a * dz + b * y + c in registers -- and writes it out once (first
+    // output-channel tile only) for the filter gradient, which therefore runs AFTER that launch.
+    // Measured per shape at the bench batch (tools/xb_bench.py, profiles/r03_xb_microbench_fp32.txt): the 1x1 data
+    // gradients pay +0.00..0.17 ms for the doubled operand load (+0.54 on the HBM-bound 256 -> 64 layer) and save an
+    // apply pass of 0.04..1.29 ms -- a gain on every conv3 and conv1; a 3x3 data gradient stages every chunk nine
+    // times (once per tap), pays +0.21..0.61 ms and saves 0.04..0.32: bn2 keeps its apply pass.
+    // (bf16: the transform is VALU-bound next to bf16 MFMAs and loses everywhere except on layer 1's 256 -> 64 data
+    // gradient, which is so HBM-bound that the saved pass still wins: -0.33 ms per launch, r03_xb_microbench_bf16.txt)
+    // (bf16, round 6: on layers 2-4 the same form runs on the 256-row kernel as an in-LDS transform of the A k-tiles
+    // (conv_p256.hip XOP) wherever that kernel takes the launch -- conv3's data gradient only: x3p)
+    bool x3, x3p;                 // bn3 -> conv3's data gradient (x3p: ... on the 256-row kernel)
+    // bn1 -> conv1's; x1d needs bn1's tile partials from the epilogue of conv2's dense data gradient.
+    // x1s: a strided conv2 runs its data gradient as parity classes, which carry no BatchNorm epilogue: there the mask comes
+    // from the stored activation a1 (kept for exactly these blocks) in that launch's epilogue, bn1's sums from a
+    // reduction pass over (dz1, y1), and the apply pass again rides in conv1's operand load
+    bool x1d, x1s;
+    bool carry;                   // conv1's data gradient (which completes d(x_in)) carries the reductions of block i-1's bn3
+    bool have_tiles;              // ... so bn3's partial sums were already produced, by block i+1's conv1 data gradient
+};
+
+// A pure function of its arguments (the dtype is the network's); training calls only -- an eval forward has no routes.
+int plan_routes(const io_net* net, int N, int S, int G, const RouteEnv& env, std::vector<BlockRoute>& out) {
+    const size_t nb = net->blocks.size();
+    const bool f32 = net->dtype == IO_F32;
+    out.assign(nb, BlockRoute{});
+    int H = S / 4, res = -1;
+    for (size_t i = 0; i < nb; ++i) {
+        const Block& b = net->blocks[i];
+        BlockRoute& r = out[i];
+        r.H = H;
+        r.Ho = H / b.stride;
+        r.Min = N * r.H * r.H;
+        r.Mout = N * r.Ho * r.Ho;
+        if (i == 0 || b.stride != 1) res += 1;       // forward order: a stride-2 block opens a new stage ...
+        r.stage = res;
+        H = r.Ho;
+        r.tiles_in = whole_tiles(r.Min, G);
+        r.tiles_out = whole_tiles(r.Mout, G);
+        r.a2_stored = !act_never_stored(net->dtype, r.Mout);
+        r.a1_stored = r.a2_stored || b.stride != 1;
+        r.bits_alloc = bits_allocated(net->dtype, r.Mout);
+        r.f3 = reads_through_bn(net->dtype, r.Mout, G);
+        r.f2 = r.f3 && b.stride == 1;
+        IO_REQUIRE((r.f2 || r.a1_stored) && (r.f3 || r.a2_stored), IO_ERR_SHAPE,
+                   "io_net_forward: G=%d does not divide this batch into whole 128-row tiles (use G in 1, 2, 4, 8)", G);
+        const bool narrow = IO_XB_BF16_L1 && b.planes <= IO_XB_BF16_MAXP;      // bf16: conv_nt_kernel's operand forms
+        const bool wide = !f32 && b.planes > IO_XB_BF16_MAXP && r.tiles_out;     // bf16: the 256-row kernel's, if it takes them
+        if (i + 1 < nb && r.tiles_out)
+            r.out_route = (f32 || narrow) ? 1
+                        : io_conv_p256_takes_xop(env, N, r.Ho, r.Ho, b.planes * 4, net->blocks[i + 1].planes, r.Mout / G) ? 2 : 0;
+        r.bits_written = r.bits_alloc && r.out_route != 1;
+        r.x3p = wide && io_conv_p256_takes_xop(env, N, r.Ho, r.Ho, b.planes * 4, b.planes, r.Mout / G);
+        r.x3 = r.tiles_out && (f32 || r.x3p || narrow);
+        r.x1d = b.stride == 1 && f32 && r.tiles_in && r.tiles_out;
+        r.x1s = b.stride != 1 && f32 && r.tiles_in && r.a1_stored;
+        r.carry = i > 0 && r.tiles_in;
+        if (i > 0) out[i - 1].have_tiles = r.carry;
+    }
+    for (BlockRoute& r : out) r.stage = res - r.stage;     // ... numbered from the back
+    IO_REQUIRE(res + 1 == kBwdStages, IO_ERR_STATE, "run_backward: %d resolution stages, expected %d", res + 1, kBwdStages);
+    return IO_OK;
+}
+
 // ---- eval mode: BatchNorm folded into the convolutions -----------------------------------------------
 // y = gamma * (conv(x, w) - mean) / sqrt(var + eps) + beta = conv(x, w * s) + (beta - mean * s), s = gamma / sqrt(var+eps):
 // one launch rewrites every filter (scaled per output channel, in the activation storage type) and every bias, then
@@ -291,6 +412,7 @@ struct Ctx {
     float* grads;
     char* ws;
     Plan plan;
+    std::vector<BlockRoute> routes;     // plan_routes, under the RouteEnv fill_ctx read once
     int N, S, G;
     int SW;                 // input width (== S except for an eval forward on a non-square input)
     bool training;
@@ -322,11 +444,17 @@ struct Ctx {
 bool stem_exact(const Ctx& c, const ConvL& L) { return L.cin_store == 8 && c.net->dtype == IO_F32; }
 
 // xf: the BatchNorm whose (training) scale / shift tables + ReLU are applied to x while it is staged
-// xr: x is the raw conv3 output of the PREVIOUS block and xr its bn3: the operand is that block's output relu(bn3(x) +
-// xr_id), evaluated while it is staged and written to xr_out (IoBwStats::xb_res)
+// xr: x is the raw conv3 output of the PREVIOUS block and xr->bn its bn3: the operand is that block's output relu(bn3(x) +
+// xr->id), evaluated while it is staged and written to xr->out (IoBwStats::xb_res)
+struct XrOperand {
+    const BnL* bn;        // nullptr: nothing pending
+    const void *y3, *id;  // the block's raw conv3 output (the x of that conv_fwd call) and its identity
+    void* out;
+    bool two;             // a block with a downsample branch: identity = bnd(yd), tables folded into plan.coef
+    uint32_t* bits;       // the one-bit mask of out, where this launch writes it (out_route 2)
+};
 int conv_fwd(const Ctx& c, const ConvL& L, const void* x, void* y, int H, bool stats = false, const BnL* xf = nullptr,
-             int Mout = 0, const BnL* xr = nullptr, const void* xr_id = nullptr, void* xr_out = nullptr,
-             bool xr_two = false, uint32_t* xr_bits = nullptr) {
+             int Mout = 0, const XrOperand* xr = nullptr) {
     IoConvGeom g = io_geom_fwd(c.N, H, H, L.cin_store, L.cout, L.k, L.k, L.stride, L.pad);
     const bool stem = L.cin_store == 8;      // the packed input x8 has the net's storage type too
     const void* w = c.wop(L.w_off);
@@ -347,17 +475,17 @@ int conv_fwd(const Ctx& c, const ConvL& L, const void* x, void* y, int H, bool s
     const bool wino = c.plan.wino_u != kNoBuf && L.k == 3 && L.stride == 1 && c.dt() == IO_F32;
     if (wino) ep.wino_u = c.buf(c.plan.wino_u);
     if (xr) {
-        Tables t = c.tables(*xr);
-        ep.xb_y = xr_id;
+        Tables t = c.tables(*xr->bn);
+        ep.xb_y = xr->id;
         ep.xb_a = t.scale;
         ep.xb_b = t.mean;
         ep.xb_c = t.shift;
-        ep.xb_out = xr_out;
+        ep.xb_out = xr->out;
         ep.xb_Mg = Mout / c.G;       // (a 1x1 stride-1 convolution: operand rows = output rows)
         ep.xb_res = 1;
-        ep.xb_bits = xr_bits;
-        if (xr_two) {                // previous block with a downsample branch: the folded tables wait in plan.coef
-            const size_t gs = (size_t)c.G * xr->C;
+        ep.xb_bits = xr->bits;
+        if (xr->two) {               // previous block with a downsample branch: the folded tables wait in plan.coef
+            const size_t gs = (size_t)c.G * xr->bn->C;
             ep.xb_a = c.buf(c.plan.coef);
             ep.xb_b = c.buf(c.plan.coef) + gs;
             ep.xb_c = c.buf(c.plan.coef) + 2 * gs;
@@ -388,61 +516,16 @@ int bn_prepare(const Ctx& c, const BnL& b, const void* y, int M, bool from_tiles
 // conv followed by the statistics of its output; the statistics ride in the conv epilogue whenever a
 // 128-row tile never straddles two BN groups
 int conv_bn(const Ctx& c, const ConvL& L, const BnL& b, const void* x, void* y, int Hin, int Mout,
-            const BnL* xf = nullptr, const BnL* xr = nullptr, const void* xr_id = nullptr, void* xr_out = nullptr,
-            bool xr_two = false, uint32_t* xr_bits = nullptr) {
+            const BnL* xf = nullptr, const XrOperand* xr = nullptr) {
     const bool fuse = c.training && (Mout / c.G) % kIoStatTileRows == 0;
-    IO_TRY(conv_fwd(c, L, x, y, Hin, fuse, xf, Mout, xr, xr_id, xr_out, xr_two, xr_bits));
+    IO_TRY(conv_fwd(c, L, x, y, Hin, fuse, xf, Mout, xr));
     return bn_prepare(c, b, y, Mout, fuse);
-}
-
-// Does conv2 / conv3 of a block with Mout output rows read its input through the producer's BatchNorm + ReLU instead of
-// from a stored activation?  fp32 with whole 128-row tiles per BatchNorm group; the forward then never writes
-// relu(bn(y)), and the backward gets it back for the one filter gradient that needs it as a side output of the
-// data-gradient launch that recomputes the ReLU mask from y anyway (IoBwStats::a_out).  (Transforming the operand of the
-// filter-gradient kernel the same way was measured: +20..35 % on the 128 x 128 tiles, which have no registers to spare.)
-// Is the output of a block with Mout rows -- out = relu(bn3(y3) + identity) -- built by the NEXT block's conv1 while it
-// stages its operand (conv_fwd's xr) instead of by a pass of its own?  fp32 (there the transform hides under the MFMAs),
-// whole 128-row tiles per group; the caller also needs an identity that is a plain tensor (no downsample branch) and a
-// next block.  Like the backward form: a 12 B / element pass becomes 8 B / element inside a GEMM.
-#ifndef IO_XB_BF16_MAXP
-#define IO_XB_BF16_MAXP 64
-#endif
-#ifndef IO_XB_BF16_L1
-#define IO_XB_BF16_L1 1   // bf16: the operand forms on the layer-1 (64-plane) blocks only
-#endif
-// Who builds the output of block i -- out = relu(bn3(y3) + identity)?  0: a BatchNorm pass of its own (bn_act); 1: the NEXT
-// block's conv1 on conv_nt_kernel's staging registers (fp32; bf16 only on the 64-plane blocks of layer 1 -- the form is VALU-bound
-// next to bf16 MFMAs, but those launches are so HBM-bound that dropping the pass still wins, as for the backward form, run_backward);
-// 2 (bf16, round 6): the next block's conv1 on the 256-row kernel, the transform applied IN LDS to every A k-tile after its DMA
-// has landed (conv_p256.hip XOP) -- that launch also writes the one-bit mask of the output.
-int out_rows(const Ctx& c, size_t i) {
-    int H = c.S / 4;
-    for (size_t k = 0; k <= i; ++k) H /= c.net->blocks[k].stride;
-    return c.N * H * H;
-}
-int xr_route(const Ctx& c, size_t i) {
-    if (!c.training || i + 1 >= c.net->blocks.size()) return 0;
-    const Block& b = c.net->blocks[i];
-    const int Mout = out_rows(c, i);
-    if (Mout % c.G != 0 || (Mout / c.G) % kIoStatTileRows != 0) return 0;
-    if (c.net->dtype == IO_F32) return 1;
-    if (IO_XB_BF16_L1 && b.planes <= IO_XB_BF16_MAXP) return 1;
-    return io_conv_p256_takes_xop(Mout, b.planes * 4, c.net->blocks[i + 1].planes, Mout / c.G) ? 2 : 0;
 }
 
 // the one-bit ReLU mask of block i's output (training plans; nullptr where the plan has none)
 uint32_t* bits_of(const Ctx& c, size_t i) {
     const size_t off = c.plan.blk[i].bits;
     return (c.training && off != kNoBuf) ? reinterpret_cast<uint32_t*>(c.ws + off) : nullptr;
-}
-
-// ... and whether the forward wrote it: block outputs built by the next block's conv1 on conv_nt_kernel have no launch that does
-bool bits_written(const Ctx& c, size_t i) {
-    return c.plan.blk[i].bits != kNoBuf && xr_route(c, i) != 1;
-}
-
-bool fuse_in(const Ctx& c, int Mout) {
-    return c.training && c.net->dtype == IO_F32 && Mout % c.G == 0 && (Mout / c.G) % kIoStatTileRows == 0;
 }
 
 int bn_act(const Ctx& c, const BnL& b, const void* y, int M, const void* idt, const BnL* b2, int relu,
@@ -539,7 +622,7 @@ int run_forward(Ctx& c, const void* x8, float* logits) {
     if (!c.training) return run_forward_eval(c, x8, logits);
     const io_net* net = c.net;
     const Plan& p = c.plan;
-    const int H0 = c.S / 2, H1 = c.S / 4;
+    const int H0 = c.S / 2;
     if (c.dt() == IO_BF16)      // bf16 GEMM operands: one cast of the whole flat fp32 parameter buffer
         IO_TRY(io_filter_prepare_t(c.params, 1, 1, (int)net->param_floats, c.act(p.wop), 0, c.st, IO_BF16));
     // stem
@@ -551,68 +634,52 @@ int run_forward(Ctx& c, const void* x8, float* logits) {
                                 c.st, c.dt(), t.scale, t.shift, c.G, t.mean));
     }
     const void* x = c.act(p.p0);
-    int H = H1;
-    // a block output whose construction was left to the next block's conv1 (xr_route): bn3, y3, identity of that block
-    const BnL* pend_bn = nullptr;
-    const void *pend_y3 = nullptr, *pend_id = nullptr;
-    bool pend_two = false;        // ... of a block with a downsample branch: identity = bnd(yd), tables folded into plan.coef
+    // a block output whose construction was left to the next block's conv1 (out_route != 0): bn3, y3, identity of that block
+    XrOperand pend{};
     for (size_t i = 0; i < net->blocks.size(); ++i) {
         const Block& b = net->blocks[i];
         const BlockBufs& bb = p.blk[i];
-        const int Ho = H / b.stride;
-        const int Min = c.N * H * H, Mout = c.N * Ho * Ho;
-        if (pend_bn) {
+        const BlockRoute& r = c.routes[i];
+        const int H = r.H, Ho = r.Ho, Min = r.Min, Mout = r.Mout;
+        if (pend.bn) {
             // x = the previous block's output does not exist yet: conv1 evaluates it from (y3, identity) on its operand
             // and writes it out (first output-channel tile); everything below that reads x comes after this launch
-            IO_TRY(conv_bn(c, b.c1, b.b1, pend_y3, c.act(bb.y1), H, Min, nullptr, pend_bn, pend_id,
-                           c.act(p.blk[i - 1].out), pend_two, xr_route(c, i - 1) == 2 ? bits_of(c, i - 1) : nullptr));
-            pend_bn = nullptr;
+            IO_TRY(conv_bn(c, b.c1, b.b1, pend.y3, c.act(bb.y1), H, Min, nullptr, &pend));
+            pend.bn = nullptr;
         } else {
             IO_TRY(conv_bn(c, b.c1, b.b1, x, c.act(bb.y1), H, Min));
         }
         // conv2 reads relu(bn1(y1)), conv3 reads relu(bn2(y2)): through the input transform straight from y1 / y2, or
-        // from a stored activation (the strided conv2 of a stage's first block keeps a1: its data gradient runs as
-        // parity classes and cannot rebuild it)
-        const bool f3 = fuse_in(c, Mout), f2 = f3 && b.stride == 1;
-        IO_REQUIRE((f2 || bb.a1 != kNoBuf) && (f3 || bb.a2 != kNoBuf), IO_ERR_SHAPE,
-                   "io_net_forward: G=%d does not divide this batch into whole 128-row tiles (use G in 1, 2, 4, 8)", c.G);
-        if (f2) {
+        // from a stored activation
+        if (r.f2) {
             IO_TRY(conv_bn(c, b.c2, b.b2, c.act(bb.y1), c.act(bb.y2), H, Mout, &b.b1));
         } else {
             IO_TRY(bn_act(c, b.b1, c.act(bb.y1), Min, nullptr, nullptr, 1, c.act(bb.a1)));
             IO_TRY(conv_bn(c, b.c2, b.b2, c.act(bb.a1), c.act(bb.y2), H, Mout));
         }
-        if (f3) {
+        if (r.f3) {
             IO_TRY(conv_bn(c, b.c3, b.b3, c.act(bb.y2), c.act(bb.y3), Ho, Mout, &b.b2));
         } else {
             IO_TRY(bn_act(c, b.b2, c.act(bb.y2), Mout, nullptr, nullptr, 1, c.act(bb.a2)));
             IO_TRY(conv_bn(c, b.c3, b.b3, c.act(bb.a2), c.act(bb.y3), Ho, Mout));
         }
-        if (b.down) {
-            IO_TRY(conv_bn(c, b.cd, b.bd, x, c.act(bb.yd), H, Mout));
-            if (xr_route(c, i)) {
-                // relu(bn3(y3) + bnd(yd)) = relu(a * y3 + b * yd + c): one table set, then as below
+        if (b.down) IO_TRY(conv_bn(c, b.cd, b.bd, x, c.act(bb.yd), H, Mout));
+        if (r.out_route) {                   // built by the next block's conv1
+            if (b.down) {
+                // relu(bn3(y3) + bnd(yd)) = relu(a * y3 + b * yd + c): one table set, then as without the branch
                 Tables t3 = c.tables(b.b3), td = c.tables(b.bd);
                 IO_TRY(io_bn_resid2_tables(t3.mean, t3.scale, t3.shift, td.mean, td.scale, td.shift, c.G, b.b3.C,
                                            c.buf(c.plan.coef), c.st));
-                pend_bn = &b.b3;
-                pend_y3 = c.act(bb.y3);
-                pend_id = c.act(bb.yd);
-                pend_two = true;
-            } else {
-                IO_TRY(bn_act(c, b.b3, c.act(bb.y3), Mout, c.act(bb.yd), &b.bd, 1, c.act(bb.out), bits_of(c, i)));
             }
-        } else if (xr_route(c, i)) {
-            pend_bn = &b.b3;                 // built by the next block's conv1
-            pend_y3 = c.act(bb.y3);
-            pend_id = x;
-            pend_two = false;
+            pend = XrOperand{&b.b3, c.act(bb.y3), b.down ? c.act(bb.yd) : x, c.act(bb.out), b.down,
+                             r.out_route == 2 ? bits_of(c, i) : nullptr};
         } else {
-            IO_TRY(bn_act(c, b.b3, c.act(bb.y3), Mout, x, nullptr, 1, c.act(bb.out), bits_of(c, i)));
+            IO_TRY(bn_act(c, b.b3, c.act(bb.y3), Mout, b.down ? c.act(bb.yd) : x, b.down ? &b.bd : nullptr, 1,
+                          c.act(bb.out), bits_of(c, i)));
         }
         x = c.act(bb.out);
-        H = Ho;
     }
+    const int H = c.routes.back().Ho;
     const float* w1 = net->n_heads > 1 ? c.params + net->fcw_off[1] : nullptr;
     const float* b1 = net->n_heads > 1 ? c.params + net->fcb_off[1] : nullptr;
     IO_TRY(io_avgpool_fc_fwd_t(x, c.N, H * H, 2048, c.params + net->fcw_off[0], c.params + net->fcb_off[0],
@@ -666,16 +733,6 @@ int conv_dgrad(const Ctx& c, const ConvL& L, const void* dy, void* dx, const voi
         IO_TRY(io_filter_prepare_t(c.params + L.w_off, L.cout, L.k * L.k, L.cin, wt, 1, c.st, c.dt()));
     return io_run_dgrad(dy, wt, dx, add, mask, c.N, H, H, L.cin, L.cout, L.k, L.k, L.stride, L.pad, c.st, bw, c.dt());
 }
-
-bool tiles_ok(const Ctx& c, int M) { return M % c.G == 0 && (M / c.G) % kIoStatTileRows == 0; }
-
-// Does the BatchNorm backward of a layer with M rows leave its apply pass to the data-gradient kernel that consumes dy
-// (IoBwStats::xb_a: dy = a * dz + b * y + c evaluated on the staged operand, written out once for the filter gradient)?
-// fp32 only: there the transform hides under the MFMAs (as the forward one does); whole 128-row tiles per group.
-// Applied: bn3 -> conv3's, bn1 -> conv1's (also of the three blocks whose conv2 is strided), the downsample BatchNorm's -> the
-// downsample convolution's data gradient, the stem's bn1 in the staging of the stem's filter gradient (stem.hip).  NOT bn2 ->
-// conv2's 3x3 data gradient (measured: a loss, see run_backward).
-bool xb_ok(const Ctx& c, int M) { return c.net->dtype == IO_F32 && tiles_ok(c, M); }
 
 IoBwStats bw_for(const Ctx& c, const BnL& b, const void* y, int M, bool mask_from_y) {
     Tables t = c.tables(b);
@@ -733,7 +790,7 @@ int bn_back_tiles(const Ctx& c, const BnL& b, const void* dz, const void* y, int
 int dgrad_then_bn(const Ctx& c, const ConvL& L, const void* dy, void* dx, int H, const BnL& b, const void* y,
                   int M, void* dyb, void* a_out = nullptr, const BnL* xb = nullptr, const void* xb_y = nullptr,
                   int xb_M = 0, void* xb_out = nullptr) {
-    if (L.stride == 1 && tiles_ok(c, M)) {
+    if (L.stride == 1 && whole_tiles(M, c.G)) {
         IoBwStats bw = bw_for(c, b, y, M, true);
         bw.a_out = a_out;
         if (xb) xb_fill(c, bw, *xb, xb_y, xb_M, xb_out);
@@ -748,25 +805,44 @@ int dgrad_then_bn(const Ctx& c, const ConvL& L, const void* dy, void* dx, int H,
     return bn_back(c, b, dx, 1, nullptr, y, M, dyb, nullptr);
 }
 
+// The backward of the stem's bn1 for a stem filter gradient that evaluates it while it stages its rows: the reduction over
+// (dz, y0) and the coefficient tables, no apply pass.  (y0 in the net's storage type; the mask is recomputed from it.)
+int stem_bn_coefs(const Ctx& c, const void* dz, IoStemXb& xb) {
+    const BnL& b = c.net->bn1;
+    Tables t = c.tables(b);
+    IO_TRY(io_bn_bwd_coefs_t(dz, c.act(c.plan.y0), c.N * (c.S / 2) * (c.S / 2), b.C, c.G, c.params + b.g_off, t.mean, t.rstd,
+                             c.grads + b.g_off, c.grads + b.b_off, c.buf(c.plan.coef), c.buf(c.plan.bn_partial),
+                             c.plan.bn_partial_floats, c.st, c.dt(), t.scale, t.shift));
+    const size_t gs = (size_t)c.G * b.C;
+    xb = IoStemXb{};
+    xb.y = (const float*)c.act(c.plan.y0);
+    xb.a = c.buf(c.plan.coef);
+    xb.b = c.buf(c.plan.coef) + gs;
+    xb.c = c.buf(c.plan.coef) + 2 * gs;
+    xb.mean = t.mean;
+    xb.scale = t.scale;
+    xb.shift = t.shift;
+    xb.G = c.G;
+    return IO_OK;
+}
+
 // Backward stages, in execution order (gradients of a stage are final when its last launch has run, so a data-parallel
 // caller can start exchanging that slice of the flat gradient buffer while the next stage computes):
 //   0 = heads + layer4, 1 = layer3, 2 = layer2, 3 = layer1 + stem.   Runs the stages [stage_lo, stage_hi).
 // Nothing is carried between calls but the workspace: which scratch buffer holds d(block output) and whether the tile
 // partials of a block's bn3 are waiting follow from the block index alone.
-constexpr int kBwdStages = 4;
 int run_backward(Ctx& c, const float* dlogits, const void* x8, int stage_lo = 0, int stage_hi = kBwdStages) {
     const io_net* net = c.net;
     const Plan& p = c.plan;
-    void* Gd = c.act(p.gbuf[0]);
-    void* Ge = c.act(p.gbuf[1]);
     void* Ga = c.act(p.gbuf[2]);
     void* Gb = c.act(p.gbuf[3]);
     void* Gc = c.act(p.gbuf[4]);
-    const int H0 = c.S / 2, H1 = c.S / 4;
-    // spatial size of the last stage
-    int Hlast = H1;
-    for (const Block& b : net->blocks) Hlast /= b.stride;
+    const int H0 = c.S / 2;
+    const int Hlast = c.routes.back().Ho;     // spatial size of the last stage
     const size_t nb = net->blocks.size();
+    // d(output of block ii) lives in gbuf[0] for the last block and the roles of gbuf[0] / gbuf[1] alternate per block:
+    // Gd of block ii (and, with ii = -1, of the max-pooling output)
+    auto dout_buf = [&](long ii) { return c.act(p.gbuf[(nb - 1 - ii) & 1]); };
     const float* w1 = net->n_heads > 1 ? c.params + net->fcw_off[1] : nullptr;
     // Gradients of block outputs are kept ALREADY MASKED by that output's ReLU: whoever writes the last
     // contribution to d(out) applies [out > 0] in its epilogue (here: the pooling backward; below: the
@@ -775,76 +851,30 @@ int run_backward(Ctx& c, const float* dlogits, const void* x8, int stage_lo = 0,
     if (stage_lo == 0)
     IO_TRY(io_avgpool_fc_bwd_t(dlogits, c.buf(p.pooled), c.N, Hlast * Hlast, 2048, c.params + net->fcw_off[0],
                                net->head_dims[0], w1, net->n_heads > 1 ? net->head_dims[1] : 0,
-                               c.act(p.blk[nb - 1].out), Gd, c.grads + net->fcw_off[0], c.grads + net->fcb_off[0],
+                               c.act(p.blk[nb - 1].out), dout_buf(nb - 1), c.grads + net->fcw_off[0], c.grads + net->fcb_off[0],
                                net->n_heads > 1 ? c.grads + net->fcw_off[1] : nullptr,
                                net->n_heads > 1 ? c.grads + net->fcb_off[1] : nullptr, c.st, c.dt()));
-    // per-block input resolution
-    std::vector<int> Hin(nb);
-    {
-        int H = H1;
-        for (size_t i = 0; i < nb; ++i) { Hin[i] = H; H /= net->blocks[i].stride; }
-    }
-    // stage of a block: the blocks of one resolution, last resolution first
-    std::vector<int> stage_of(nb);
-    {
-        int st = kBwdStages, res = -1;
-        for (size_t i = 0; i < nb; ++i) {                    // forward order: a stride-2 block opens a new stage ...
-            if (i == 0 || net->blocks[i].stride != 1) res += 1;
-            stage_of[i] = res;
-        }
-        for (size_t i = 0; i < nb; ++i) stage_of[i] = res - stage_of[i];     // ... numbered from the back
-        st = res + 1;
-        IO_REQUIRE(st == kBwdStages, IO_ERR_STATE, "run_backward: %d resolution stages, expected %d", st, kBwdStages);
-    }
-    bool have_tiles = false;    // BN-backward partial sums of the current block's bn3 already produced?
     for (size_t ii = nb; ii-- > 0;) {
         const Block& b = net->blocks[ii];
         const BlockBufs& bb = p.blk[ii];
-        const int H = Hin[ii], Ho = H / b.stride;
-        const int Min = c.N * H * H, Mout = c.N * Ho * Ho;
-        if (stage_of[ii] < stage_lo || stage_of[ii] >= stage_hi) {
-            // not ours: only keep the bookkeeping in step (buffer roles alternate per block; the carry rule of below)
-            have_tiles = ii > 0 && tiles_ok(c, Min);
-            void* t = Gd; Gd = Ge; Ge = t;
-            continue;
-        }
+        const BlockRoute& r = c.routes[ii];
+        if (r.stage < stage_lo || r.stage >= stage_hi) continue;
+        const int H = r.H, Ho = r.Ho, Min = r.Min, Mout = r.Mout;
+        void *Gd = dout_buf((long)ii), *Ge = dout_buf((long)ii - 1);
         const void* xin = ii == 0 ? c.act(p.p0) : c.act(p.blk[ii - 1].out);
         // the block input is the previous block's post-ReLU output (for block 0 it is the max-pool output,
         // whose gradient is not masked here)
         const void* xmask = ii == 0 ? nullptr : xin;
-        // bn3: Gd holds dz = d(out) * [out > 0]; dy3 -> Ga
-        // Where xb_ok, the apply pass of a BatchNorm backward (read dz, read y, write dy) does not exist: the reductions
-        // become three coefficient tables and the data-gradient launch that consumes dy evaluates it on its operand --
-        // dz and y are loaded side by side, dy = a * dz + b * y + c in registers -- and writes it out once (first
-        // output-channel tile only) for the filter gradient, which therefore runs AFTER that launch.
-        // Measured per shape at the bench batch (tools/xb_bench.py, profiles/r03_xb_microbench_fp32.txt): the 1x1 data
-        // gradients pay +0.00..0.17 ms for the doubled operand load (+0.54 on the HBM-bound 256 -> 64 layer) and save an
-        // apply pass of 0.04..1.29 ms -- a gain on every conv3 and conv1; a 3x3 data gradient stages every chunk nine
-        // times (once per tap), pays +0.21..0.61 ms and saves 0.04..0.32: bn2 keeps its apply pass.
-        // (bf16: the transform is VALU-bound next to bf16 MFMAs and loses everywhere except on layer 1's 256 -> 64 data
-        // gradient, which is so HBM-bound that the saved pass still wins: -0.33 ms per launch, r03_xb_microbench_bf16.txt)
-        // (bf16, round 6: on layers 2-4 the same form runs on the 256-row kernel as an in-LDS transform of the A k-tiles
-        // (conv_p256.hip XOP) wherever that kernel takes the launch -- conv3's data gradient only: x3p)
-        const bool x3p = c.net->dtype == IO_BF16 && b.planes > IO_XB_BF16_MAXP && tiles_ok(c, Mout) &&
-                         io_conv_p256_takes_xop(Mout, b.planes * 4, b.planes, Mout / c.G);
-        const bool x3 = xb_ok(c, Mout) || x3p ||                 // bn3 -> conv3's data gradient
-                        (IO_XB_BF16_L1 && c.net->dtype == IO_BF16 && b.planes <= IO_XB_BF16_MAXP && tiles_ok(c, Mout));
-        const bool f3 = fuse_in(c, Mout), f2 = f3 && b.stride == 1;
-        // bn1 -> conv1's; needs bn1's tile partials from the epilogue of conv2's dense data gradient
-        const bool x1d = b.stride == 1 && xb_ok(c, Min) && tiles_ok(c, Mout);
-        // a strided conv2 runs its data gradient as parity classes, which carry no BatchNorm epilogue: there the mask comes
-        // from the stored activation a1 (kept for exactly these blocks) in that launch's epilogue, bn1's sums from a
-        // reduction pass over (dz1, y1), and the apply pass again rides in conv1's operand load
-        const bool x1s = b.stride != 1 && xb_ok(c, Min) && bb.a1 != kNoBuf;
+        // bn3: Gd holds dz = d(out) * [out > 0]; dy3 -> Ga  (which BatchNorm backward keeps its apply pass: BlockRoute)
+        const bool x3 = r.x3, x3p = r.x3p, f3 = r.f3, f2 = r.f2, x1d = r.x1d, x1s = r.x1s;
         const bool x1 = x1d || x1s;
         if (x3)
-            IO_TRY(bn_back_coefs(c, b.b3, Gd, c.act(bb.y3), Mout, have_tiles));
-        else if (have_tiles)
+            IO_TRY(bn_back_coefs(c, b.b3, Gd, c.act(bb.y3), Mout, r.have_tiles));
+        else if (r.have_tiles)
             IO_TRY(bn_back_tiles(c, b.b3, Gd, c.act(bb.y3), Mout, Ga));
         else
             IO_TRY(bn_back(c, b.b3, Gd, 0, nullptr, c.act(bb.y3), Mout, Ga, nullptr));
-        have_tiles = false;
-        // Where the forward read relu(bn(y)) through the input transform (fuse_in) that activation was never stored: the
+        // Where the forward read relu(bn(y)) through the input transform (f2 / f3) that activation was never stored: the
         // data-gradient launch, which recomputes the ReLU mask from y anyway, rebuilds it into the one `aside` buffer, and
         // the filter gradient that needs it runs right after (instead of right before) that launch.
         void* As = f3 ? c.act(p.aside) : nullptr;
@@ -890,21 +920,20 @@ int run_backward(Ctx& c, const float* dlogits, const void* x8, int stage_lo = 0,
         if (x1) IO_TRY(bn_back_coefs(c, b.b1, Ga, c.act(bb.y1), Min, x1d));
         {
             IoBwStats bw{};
-            const bool carry = ii > 0 && tiles_ok(c, Min);
+            const bool carry = r.carry;
             if (carry) bw = bw_for(c, net->blocks[ii - 1].b3, c.act(p.blk[ii - 1].y3), Min, false);
             if (x1) xb_fill(c, bw, b.b1, c.act(bb.y1), Min, Gb);
             // [x_in > 0] also as one bit per element where the forward left it: the 256-row kernel reads that instead of the
             // tensor (4 of the 17 bytes per element this launch moves in bf16); conv_nt_kernel ignores it
-            const uint32_t* mbits = (ii > 0 && xmask && bits_written(c, ii - 1)) ? bits_of(c, ii - 1) : nullptr;
+            const uint32_t* mbits = (ii > 0 && c.routes[ii - 1].bits_written) ? bits_of(c, ii - 1) : nullptr;
             if (mbits) bw.maskbits = mbits;
             IO_TRY(conv_dgrad(c, b.c1, x1 ? Ga : Gb, Ge, partial, xmask, H, (carry || x1 || mbits) ? &bw : nullptr));
-            have_tiles = carry;
         }
         if (x1) IO_TRY(conv_wgrad(c, b.c1, xin, Gb, H));
-        void* t = Gd; Gd = Ge; Ge = t;
     }
     if (stage_hi < kBwdStages) return IO_OK;
     // Gd = d(maxpool output)
+    void *Gd = dout_buf(-1), *Ge = dout_buf(0);
     IO_TRY(io_maxpool_bwd_t(Gd, reinterpret_cast<const uint32_t*>(c.ws + p.idx0), c.N, H0, H0, 64, Ge, c.st, c.dt()));
     // stem filter gradient only: the network input needs no data gradient -- so bn1's backward has ONE reader, and on
     // the row-persistent kernel it is evaluated while that reader stages its rows (no apply pass: reduction + tables only)
@@ -912,21 +941,8 @@ int run_backward(Ctx& c, const float* dlogits, const void* x8, int stage_lo = 0,
         IoConvGeom g = io_geom_fwd(c.N, c.S, c.S, 8, 64, 7, 7, 2, 3);
         g.cr = net->stem.cin;
         if (stem_exact(c, net->stem) && io_stem_rows_ok(g) && c.N % c.G == 0) {
-            const BnL& b = net->bn1;
-            Tables t = c.tables(b);
-            IO_TRY(io_bn_bwd_coefs_t(Ge, c.act(p.y0), c.N * H0 * H0, b.C, c.G, c.params + b.g_off, t.mean, t.rstd,
-                                     c.grads + b.g_off, c.grads + b.b_off, c.buf(c.plan.coef), c.buf(c.plan.bn_partial),
-                                     c.plan.bn_partial_floats, c.st, c.dt(), t.scale, t.shift));
-            const size_t gs = (size_t)c.G * b.C;
-            IoStemXb xb{};
-            xb.y = (const float*)c.act(p.y0);
-            xb.a = c.buf(c.plan.coef);
-            xb.b = c.buf(c.plan.coef) + gs;
-            xb.c = c.buf(c.plan.coef) + 2 * gs;
-            xb.mean = t.mean;
-            xb.scale = t.scale;
-            xb.shift = t.shift;
-            xb.G = c.G;
+            IoStemXb xb;
+            IO_TRY(stem_bn_coefs(c, Ge, xb));
             IO_TRY(io_launch_stem_wgrad_rows(g, (const float*)x8, (const float*)Ge, c.buf(c.plan.stem_dwp),
                                              c.buf(c.plan.wg_partial), c.plan.wg_partial_bytes, c.st, &xb));
             return io_stem_unpack_grad(c.buf(c.plan.stem_dwp), c.grads + net->stem.w_off, net->stem.cout, 49,
@@ -937,21 +953,8 @@ int run_backward(Ctx& c, const float* dlogits, const void* x8, int stage_lo = 0,
     if (c.net->dtype == IO_BF16) {
         IoConvGeom g = io_geom_fwd(c.N, c.S, c.S, 8, 64, 7, 7, 2, 3);
         if (io_stem_wgrad_halo_ok(g, c.plan.wg_partial_bytes, c.G)) {
-            const BnL& b = net->bn1;
-            Tables t = c.tables(b);
-            IO_TRY(io_bn_bwd_coefs_t(Ge, c.act(p.y0), c.N * H0 * H0, b.C, c.G, c.params + b.g_off, t.mean, t.rstd,
-                                     c.grads + b.g_off, c.grads + b.b_off, c.buf(c.plan.coef), c.buf(c.plan.bn_partial),
-                                     c.plan.bn_partial_floats, c.st, c.dt(), t.scale, t.shift));
-            const size_t gs = (size_t)c.G * b.C;
-            IoStemXb xb{};
-            xb.y = (const float*)c.act(p.y0);        // (bf16 storage)
-            xb.a = c.buf(c.plan.coef);
-            xb.b = c.buf(c.plan.coef) + gs;
-            xb.c = c.buf(c.plan.coef) + 2 * gs;
-            xb.mean = t.mean;
-            xb.scale = t.scale;
-            xb.shift = t.shift;
-            xb.G = c.G;
+            IoStemXb xb;
+            IO_TRY(stem_bn_coefs(c, Ge, xb));
             return io_launch_stem_wgrad_halo(g, x8, Ge, c.grads + net->stem.w_off, c.buf(c.plan.wg_partial),
                                              c.plan.wg_partial_bytes, c.st, &xb);
         }
@@ -1078,8 +1081,9 @@ extern "C" long io_net_activation_offset(const io_net* net, int N, int S, int wh
     return -1;
 }
 
-static void fill_ctx(Ctx& c, io_net* net, const float* params, float* running, float* grads, int N, int S, int G,
-                     bool training, void* ws, hipStream_t st, int SW = 0) {
+// (the one place an entry point reads the switches and the device: every route of the call follows from this RouteEnv)
+static int fill_ctx(Ctx& c, io_net* net, const float* params, float* running, float* grads, int N, int S, int G,
+                    bool training, void* ws, hipStream_t st, int SW = 0) {
     c.net = net;
     c.params = params;
     c.running = running;
@@ -1102,6 +1106,27 @@ static void fill_ctx(Ctx& c, io_net* net, const float* params, float* running, f
     }
     long acc = 0;
     for (int i = 0; i < net->n_bn; ++i) { c.chan_prefix[i] = acc; acc += Cs[i]; }
+    return training ? plan_routes(net, N, S, G, io_route_env_now(), c.routes) : IO_OK;
+}
+
+// One word per Bottleneck block (bit positions: include/instaorder_hip.h); the environment comes in as arguments, so this
+// launches nothing and needs no device.
+extern "C" int io_net_step_routes(const io_net* net, int N, int S, int G, int p256_mode, int xop, int ncu, int32_t* out,
+                                  int max_blocks) {
+    IO_TRY(check_shape(N, S, G));
+    IO_REQUIRE(ncu >= 1 && out && max_blocks >= (int)net->blocks.size(), IO_ERR_SHAPE,
+               "io_net_step_routes: ncu=%d, room for %d of %d blocks", ncu, out ? max_blocks : 0, (int)net->blocks.size());
+    std::vector<BlockRoute> rt;
+    IO_TRY(plan_routes(net, N, S, G, RouteEnv{p256_mode, xop, ncu}, rt));
+    for (size_t i = 0; i < rt.size(); ++i) {
+        const BlockRoute& r = rt[i];
+        const bool f[14] = {r.tiles_in, r.tiles_out, r.f2, r.f3, r.bits_written, r.x3, r.x3p, r.x1d, r.x1s, r.carry,
+                            r.have_tiles, r.a1_stored, r.a2_stored, r.bits_alloc};
+        int32_t w = r.out_route | (r.stage << 16);
+        for (int k = 0; k < 14; ++k) w |= (int32_t)f[k] << (2 + k);
+        out[i] = w;
+    }
+    return (int)rt.size();
 }
 
 extern "C" int io_net_forward(io_net* net, const float* params, float* running, const void* x8, int N, int S,
@@ -1109,7 +1134,7 @@ extern "C" int io_net_forward(io_net* net, const float* params, float* running, 
     IO_TRY(check_shape(N, S, G));
     IO_REQUIRE(training || G == 1, IO_ERR_SHAPE, "eval forward uses running statistics: G must be 1");
     Ctx c;
-    fill_ctx(c, net, params, running, nullptr, N, S, G, training != 0, ws, st);
+    IO_TRY(fill_ctx(c, net, params, running, nullptr, N, S, G, training != 0, ws, st));
     IO_REQUIRE(ws_bytes >= c.plan.total, IO_ERR_WORKSPACE, "io_net_forward: workspace %zu < %zu bytes", ws_bytes,
                c.plan.total);
     return run_forward(c, x8, logits);
@@ -1131,7 +1156,7 @@ extern "C" int io_net_forward_eval_hw(io_net* net, const float* params, float* r
                                       int W, void* ws, size_t ws_bytes, float* logits, hipStream_t st) {
     IO_TRY(check_shape_hw(N, H, W));
     Ctx c;
-    fill_ctx(c, net, params, running, nullptr, N, H, 1, false, ws, st, W);
+    IO_TRY(fill_ctx(c, net, params, running, nullptr, N, H, 1, false, ws, st, W));
     IO_REQUIRE(ws_bytes >= c.plan.total, IO_ERR_WORKSPACE, "io_net_forward_eval_hw: workspace %zu < %zu bytes", ws_bytes,
                c.plan.total);
     return run_forward_eval(c, x8, logits);
@@ -1142,7 +1167,7 @@ extern "C" int io_net_backward(io_net* net, const float* params, float* grads, c
                                hipStream_t st) {
     IO_TRY(check_shape(N, S, G));
     Ctx c;
-    fill_ctx(c, net, params, nullptr, grads, N, S, G, true, ws, st);
+    IO_TRY(fill_ctx(c, net, params, nullptr, grads, N, S, G, true, ws, st));
     IO_REQUIRE(ws_bytes >= c.plan.total, IO_ERR_WORKSPACE, "io_net_backward: workspace %zu < %zu bytes", ws_bytes,
                c.plan.total);
     return run_backward(c, dlogits, x8);
@@ -1155,7 +1180,7 @@ extern "C" int io_net_backward_stages(io_net* net, const float* params, float* g
     IO_REQUIRE(stage_lo >= 0 && stage_lo < stage_hi && stage_hi <= kBwdStages, IO_ERR_SHAPE,
                "io_net_backward_stages: stages [%d, %d) outside [0, %d)", stage_lo, stage_hi, kBwdStages);
     Ctx c;
-    fill_ctx(c, net, params, nullptr, grads, N, S, G, true, ws, st);
+    IO_TRY(fill_ctx(c, net, params, nullptr, grads, N, S, G, true, ws, st));
     IO_REQUIRE(ws_bytes >= c.plan.total, IO_ERR_WORKSPACE, "io_net_backward_stages: workspace %zu < %zu bytes", ws_bytes,
                c.plan.total);
     return run_backward(c, dlogits, x8, stage_lo, stage_hi);
