@@ -792,6 +792,56 @@ int io_jpeg_set_images_per_wave(int images);
 int io_jpeg_get_images_per_wave(void);
 int io_jpeg_lds_table_sets(void);   /* IO_JPEG_LDS_TABLE_SETS of the built library */
 
+/* ---- PNG images and 16-bit depth maps decoded on the device (csrc/png.hip, csrc/png_inflate.h, DESIGN.md "PNG images"),
+ * in front of io_pair_planes_u8_hw or of io_depth_errors_median.  The caller parses the chunks; what travels is the zlib
+ * stream of every image (its IDAT payloads concatenated) WITHOUT its two header bytes and its Adler-32 trailer, in one byte
+ * pool, and one descriptor per image that carries the trailer's word.  One call decodes n non-interlaced images, which may
+ * differ in size and form, to byte offsets of `out`:
+ *   channels 3 / depth 8 (RGB)   uint8 H x W x 3, copied
+ *   channels 4 / depth 8 (RGBA)  uint8 H x W x 3, alpha dropped
+ *   channels 1 / depth 8 (gray)  uint8 H x W x 3, R = G = B
+ *   channels 1 / depth 16        uint16 H x W in host byte order ("raw16": depth ground truth); out_off must be even
+ * 8-bit outputs may sit at any alignment (stores of at most 4 bytes) and no byte outside [out_off, out_off + size) is
+ * touched.  The result is RFC 1950 / 1951 / 2083 with zlib's acceptance rules, in integers.
+ *   Three stages behind an offset launch: (1) inflate, one wave per image, the symbol loop uniform over the wave with its
+ * code tables and the last 32 KiB of output in LDS (36.8 KiB per image), to the filtered scanlines in the workspace, then
+ * Adler-32 of those bytes, one block per image; (2) unfilter in place, one wave per image, a skewed wavefront over bands
+ * of 64 rows (io_png_band_rows); (3) pack, one thread per aligned 4-byte word of the output.  status_dev[i] (int32,
+ * written by the call's kernels) is 0 for a decoded image, otherwise the first of
+ *   1 block type 3;  2 stored length and its complement disagree;  3 an invalid code-length set by zlib's inflate_table
+ *   rules (over-subscribed; incomplete other than a single 1-bit literal/length or distance code; no end-of-block code;
+ *   HLIT > 286; HDIST > 30; a repeat with nothing to repeat or running past the set);  4 bits that are no code of an
+ *   incomplete set, a literal/length symbol above 285 or a distance symbol above 29;  5 a distance reaching before the
+ *   first output byte;  6 data exhausted before the end of the final block;  7 the stream yields more or fewer bytes
+ *   than H (1 + rowbytes);  8 Adler-32 mismatch;  9 a filter byte above 4.
+ * A failed image's slot has unspecified contents (a later stage leaves it alone); no other image and no byte outside the
+ * slot is affected.  Data after the end of the final block is ignored.
+ *   desc_dev / desc_host are the same table in device and host memory; the host copy is validated before anything is
+ * enqueued: 1 <= H, W <= 65535 and 3 H W < 2^31, the channels / depth pairs above, data range inside pool_bytes, output
+ * inside out_bytes, raw16 output 2-byte aligned, n <= 65535, workspace 16-byte and descriptors 8-byte aligned
+ * (IO_ERR_SHAPE otherwise; IO_ERR_WORKSPACE for a workspace below io_png_workspace_bytes()).  The kernels are safe
+ * whatever the pool BYTES are: the symbol loop consumes at least one bit per iteration and ends at data_bytes or at the
+ * expected output size, the code-length loops end at 320 entries, reads stay inside the image's data range and stores
+ * inside its workspace range and output slot.
+ *   Workspace: one offset per image and H (1 + rowbytes) bytes per image, each rounded up to 16.  Nothing is kept between
+ * calls. */
+typedef struct io_png_desc {
+    int64_t data_off;     /* first byte of the zlib stream (after its 2 header bytes) in the pool */
+    int64_t out_off;      /* byte offset of the output image */
+    int32_t data_bytes;   /* DEFLATE bytes, Adler-32 trailer excluded */
+    int32_t H, W;
+    int32_t channels;     /* samples per pixel in the file: 1, 3 or 4 */
+    int32_t depth;        /* 8, or 16 with channels == 1 */
+    uint32_t adler;       /* expected Adler-32 of the inflated bytes */
+    int32_t reserved[2];
+} io_png_desc;
+/* 0 = descriptors the call would refuse (io_last_error_string says why); never 0 for valid ones */
+size_t io_png_workspace_bytes(const io_png_desc* desc_host, int n);
+int io_png_decode(const uint8_t* pool_dev, size_t pool_bytes, const io_png_desc* desc_dev, const io_png_desc* desc_host,
+                  int n, uint8_t* out, size_t out_bytes, void* workspace, size_t workspace_bytes, int32_t* status_dev,
+                  hipStream_t stream);
+int io_png_band_rows(void);   /* rows per band of the unfilter stage in the built library */
+
 /* ---- measurement aid (bench.py): HIP-event timing of every launch, per kernel class, on the launch
  * stream.  Process-global; io_prof_end synchronises on the recorded events and returns the number of
  * classes written.  flops / bytes are the ALGORITHMIC figures of the timed launches (the direct convolution's count). */

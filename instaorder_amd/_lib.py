@@ -66,6 +66,13 @@ class JpegDesc(C.Structure):
                 ("ac", C.c_uint8 * 4), ("reserved", C.c_int32)]
 
 
+class PngDesc(C.Structure):
+    """io_png_desc of include/instaorder_hip.h"""
+    _fields_ = [("data_off", C.c_int64), ("out_off", C.c_int64), ("data_bytes", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("channels", C.c_int32), ("depth", C.c_int32), ("adler", C.c_uint32),
+                ("reserved", C.c_int32 * 2)]
+
+
 class DgradFused(C.Structure):
     """io_dgrad_fused of include/instaorder_hip.h (device pointers as integers, None = NULL)"""
     _fields_ = [(n, C.c_void_p) for n in ("xb_y", "xb_coef", "xb_dy_out", "add", "relu_mask", "ep_y", "ep_mean", "ep_rstd",
@@ -140,6 +147,10 @@ SIGNATURES = {
     "io_jpeg_set_images_per_wave": (_I, [_I]),
     "io_jpeg_get_images_per_wave": (_I, []),
     "io_jpeg_lds_table_sets": (_I, []),
+    # pool_dev, pool_bytes, desc_dev, desc_host, n, out, out_bytes, workspace, workspace_bytes, status_dev, stream
+    "io_png_decode": (_I, [_P, _Z, _P, _P, _I, _P, _Z, _P, _Z, _P, _P]),
+    "io_png_workspace_bytes": (_Z, [_P, _I]),
+    "io_png_band_rows": (_I, []),
     "io_order_loss": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _F, _F, _F, _P, _P, _P]),
     "io_sgd_momentum": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P]),
     # params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, stream

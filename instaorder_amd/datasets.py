@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .jpeg import is_jpeg
+from .png import is_png
 from .rle import is_encoded
 
 INTER_LINEAR, INTER_CUBIC, INTER_CUBIC_F64 = 1, 2, 3     # io_pair_desc.interp
@@ -87,7 +88,7 @@ class PairRenderer(object):
         self._pinned = [None, None]
         self._events = [None, None]
         self._turn = 0
-        self._status = [None, None]  # per staging slot: (pinned int32 status words of the JPEG decode, the images' names)
+        self._status = [None, None]  # per staging slot: [(pinned int32 status words of a JPEG / PNG decode, the images, jpeg / png)]
         self.last_upload = None      # bytes the last render() sent to the device: images / masks (or run tables, vertices) / descriptors
 
     def _staging(self, nbytes):
@@ -102,15 +103,15 @@ class PairRenderer(object):
         return k, self._pinned[k]
 
     def _check_slot(self, k):
-        """the JPEG status words of the batch that used staging slot k (its event has been waited for)"""
+        """the JPEG and PNG status words of the batch that used staging slot k (its event has been waited for)"""
         if self._status[k] is not None:
-            words, images = self._status[k]
+            pending = self._status[k]
             self._status[k] = None
-            from . import jpeg
-            jpeg.raise_for_status(words.numpy(), images)
+            for words, images, codec in pending:
+                codec.raise_for_status(words.numpy(), images)
 
     def check_status(self):
-        """Waits for the batches still in flight and raises RuntimeError naming a JPEG image that did not decode.  render()
+        """Waits for the batches still in flight and raises RuntimeError naming a JPEG or PNG image that did not decode.  render()
         reports such an image by itself when its staging slot comes round again, two batches later; this is for the end
         of a run (``BatchPrefetcher`` calls it)."""
         for k in (0, 1):
@@ -123,6 +124,9 @@ class PairRenderer(object):
         n, H, W = masks[ii].shape
         if not is_encoded(masks[ii]) and masks[ii].dtype != np.uint8:
             raise TypeError("instance masks must be uint8 (got %s)" % masks[ii].dtype)
+        if load_rgb and is_png(images[ii]) and images[ii].raw16:
+            raise ValueError("image %d (%s) is a 16-bit grayscale PNG: a depth map (png.decode gives its values), not a "
+                             "picture the renderer takes" % (ii, images[ii].name))
         if load_rgb and (images[ii].shape != (H, W, 3) or images[ii].dtype != np.uint8):
             raise ValueError("image %d: expected uint8 [%d,%d,3], got %s %s" % (ii, H, W, images[ii].dtype,
                                                                                images[ii].shape))
@@ -164,13 +168,13 @@ class PairRenderer(object):
         return rgb, m1, m2
 
     def render(self, images, masks, items, load_rgb=True):
-        """images: list of uint8 [H,W,3] arrays or ``jpeg.JpegImage`` (entries may be None when load_rgb is False); masks: list of uint8
+        """images: list of uint8 [H,W,3] arrays, ``jpeg.JpegImage`` or 8-bit ``png.PngImage`` (entries may be None when load_rgb is False); masks: list of uint8
         [n,H,W] arrays, ``rle.RLEMasks`` or ``poly.PolyMasks``, one per image; items: list of (image_index, idx1, idx2,
         (x, y, w, h), interp, flip)."""
         P = len(items)
         if P == 0:
             raise ValueError("PairRenderer.render: empty batch")
-        if any(is_encoded(m) for m in masks) or (load_rgb and any(is_jpeg(im) for im in images)):
+        if any(is_encoded(m) for m in masks) or (load_rgb and any(is_jpeg(im) or is_png(im) for im in images)):
             return self._render_rle(images, masks, items, load_rgb)
         # arena layout: every referenced image once, every referenced mask once (16-byte aligned)
         off, cursor = {}, 0
@@ -204,15 +208,15 @@ class PairRenderer(object):
 
     def _render_rle(self, images, masks, items, load_rgb):
         """render() for a batch in which at least one image carries ``rle.RLEMasks`` or ``poly.PolyMasks``, or is a
-        ``jpeg.JpegImage``.  The arena lives on the device and only part of it is uploaded: one device buffer [array images
+        ``jpeg.JpegImage`` or a ``png.PngImage``.  The arena lives on the device and only part of it is uploaded: one device buffer [array images
         and dense masks | run tables | decode descriptors | vertices | part and mask descriptors | entropy bytes | JPEG
-        tables and descriptors | pair descriptors | decoded masks and images | polygon workspace | JPEG workspace and
-        status], of which everything before the decoded part comes through the pinned staging buffer in one copy.  One
+        tables and descriptors | PNG stream bytes and descriptors | pair descriptors | decoded masks and images | polygon
+        workspace | JPEG workspace and status | PNG workspace and status], of which everything before the decoded part comes through the pinned staging buffer in one copy.  One
         ``io_rle_decode_u8`` launch fills the slot of every referenced run-length mask, one ``io_poly_fill_u8`` call the
         slot of every referenced polygon instance and one ``io_jpeg_decode_u8`` call the slot of every referenced JPEG
-        image, then ``io_pair_planes_u8_hw`` runs on the arena as it does for dense arrays.  (A batch without polygons or
-        JPEG images has empty regions for them: the layout of the run-length path as it was.)"""
-        from . import jpeg, poly, rle
+        image and one ``io_png_decode`` call the slot of every referenced PNG image, then ``io_pair_planes_u8_hw`` runs on the arena as it does for dense arrays.  (A batch without polygons,
+        JPEG or PNG images has empty regions for them: the layout of the run-length path as it was.)"""
+        from . import jpeg, png, poly, rle
         P = len(items)
         up, dec = {}, {}                     # key -> offset inside its region
         cursors = {id(up): 0, id(dec): 0}
@@ -230,13 +234,17 @@ class PairRenderer(object):
         for ii, i1, i2, box, interp, flip in items:
             n, H, W = self._check_item(images, masks, ii, load_rgb)
             region = dec if is_encoded(masks[ii]) else up
-            keys.append((place(dec if is_jpeg(images[ii]) else up, ("img", ii), H * W * 3) if load_rgb else None, region,
+            keys.append((place(dec if is_jpeg(images[ii]) or is_png(images[ii]) else up, ("img", ii), H * W * 3) if load_rgb else None, region,
                          place(region, ("m", ii, range(n)[int(i1)]), H * W),
                          place(region, ("m", ii, range(n)[int(i2)]), H * W)))
         # an instance of the decoded region is a run-length code (of RLEMasks, or one inside PolyMasks) or a polygon
         refs = [(key, (masks[key[1]], key[2]) if isinstance(masks[key[1]], rle.RLEMasks) else masks[key[1]].rle_ref(key[2]))
                 for key in dec if key[0] == "m"]
-        jp_keys = [key for key in dec if key[0] == "img"]
+        jp_keys = [key for key in dec if key[0] == "img" and is_jpeg(images[key[1]])]
+        pg_keys = [key for key in dec if key[0] == "img" and is_png(images[key[1]])]
+        gpool, gdesc = png.descriptors([images[k[1]] for k in pg_keys], [0] * len(pg_keys)) if pg_keys else (
+            np.zeros(0, np.uint8), ())
+        gdbytes = C.sizeof(gdesc) if pg_keys else 0
         jpool, jtabs, jdesc = jpeg.descriptors([images[k[1]] for k in jp_keys], [0] * len(jp_keys)) if jp_keys else (
             np.zeros(0, np.uint8), np.zeros(0, np.uint8), ())
         jdbytes = C.sizeof(jdesc) if jp_keys else 0
@@ -254,7 +262,9 @@ class PairRenderer(object):
         jp_at = pm_at + (pbytes[1] + 15) // 16 * 16
         jt_at = jp_at + (jpool.size + 15) // 16 * 16
         jd_at = jt_at + (jtabs.size + 15) // 16 * 16
-        pd_at = jd_at + (jdbytes + 15) // 16 * 16
+        gp_at = jd_at + (jdbytes + 15) // 16 * 16
+        gd_at = gp_at + (gpool.size + 15) // 16 * 16
+        pd_at = gd_at + (gdbytes + 15) // 16 * 16
         dec_at = pd_at + (C.sizeof(desc) + 15) // 16 * 16             # = the bytes that are uploaded
         nbytes = dec_at + max(cursors[id(dec)], 16)
         ws_at = (nbytes + 15) // 16 * 16
@@ -265,10 +275,18 @@ class PairRenderer(object):
             pmasks[k].out_off = dec_at + dec[key]
         for k, key in enumerate(jp_keys):
             jdesc[k].out_off = dec_at + dec[key]
+        for k, key in enumerate(pg_keys):
+            gdesc[k].out_off = dec_at + dec[key]
         jws_at = (ws_at + ws_bytes + 15) // 16 * 16
         jent = jpeg.get_entropy()                                    # the stage jpeg.set_entropy names sizes the arena ...
         jws_bytes = jpeg.workspace_bytes(jdesc, jent) if jp_keys else 0
         st_at = jws_at + jws_bytes
+        end = st_at + 4 * len(jp_keys) if jp_keys else (ws_at + ws_bytes if pol_keys else nbytes)
+        gws_at = (end + 15) // 16 * 16
+        gws_bytes = png.workspace_bytes(gdesc) if pg_keys else 0
+        gst_at = gws_at + gws_bytes
+        if pg_keys:
+            end = gst_at + 4 * len(pg_keys)
         for k, ((ii, i1, i2, box, interp, flip), (kimg, region, k1, k2)) in enumerate(zip(items, keys)):
             base = dec_at if region is dec else 0
             _, H, W = masks[ii].shape
@@ -288,14 +306,16 @@ class PairRenderer(object):
             host[jp_at:jp_at + jpool.size] = jpool
             host[jt_at:jt_at + jtabs.size] = jtabs
             host[jd_at:jd_at + jdbytes] = np.frombuffer(jdesc, dtype=np.uint8)
+        if pg_keys:
+            host[gp_at:gp_at + gpool.size] = gpool
+            host[gd_at:gd_at + gdbytes] = np.frombuffer(gdesc, dtype=np.uint8)
         host[pd_at:pd_at + C.sizeof(desc)] = np.frombuffer(desc, dtype=np.uint8)
-        dev = torch.empty(st_at + 4 * len(jp_keys) if jp_keys else (ws_at + ws_bytes if pol_keys else nbytes),
-                          dtype=torch.uint8, device=self.device)
+        dev = torch.empty(end, dtype=torch.uint8, device=self.device)
         dev[:dec_at].copy_(stage[:dec_at], non_blocking=True)
         stream = torch.cuda.current_stream(self.device)
         self._upload_done(slot, stream)
-        self.last_upload = dict(images=sent["img"] + jpool.size + jtabs.size, masks=sent["m"] + ends.nbytes + verts.nbytes,
-                                descriptors=C.sizeof(rdesc) + sum(pbytes) + jdbytes + C.sizeof(desc), total=dec_at)
+        self.last_upload = dict(images=sent["img"] + jpool.size + jtabs.size + gpool.size, masks=sent["m"] + ends.nbytes + verts.nbytes,
+                                descriptors=C.sizeof(rdesc) + sum(pbytes) + jdbytes + gdbytes + C.sizeof(desc), total=dec_at)
         base = dev.data_ptr()
         if jp_keys:
             # ... and is the entry point called: io_jpeg_decode_u8 or io_jpeg_decode_par_u8
@@ -304,7 +324,14 @@ class PairRenderer(object):
             # the status words follow the batch to pinned memory; they are read when this staging slot comes round again
             words = torch.empty(len(jp_keys), dtype=torch.int32).pin_memory()
             words.copy_(dev[st_at:st_at + 4 * len(jp_keys)].view(torch.int32), non_blocking=True)
-            self._status[slot] = (words, [images[k[1]] for k in jp_keys])
+            self._status[slot] = [(words, [images[k[1]] for k in jp_keys], jpeg)]
+            self._upload_done(slot, stream)
+        if pg_keys:
+            png.launch(base + gp_at, gpool.size, base + gd_at, gdesc, base, nbytes, base + gws_at, gws_bytes, base + gst_at,
+                       stream.cuda_stream)
+            words = torch.empty(len(pg_keys), dtype=torch.int32).pin_memory()
+            words.copy_(dev[gst_at:gst_at + 4 * len(pg_keys)].view(torch.int32), non_blocking=True)
+            self._status[slot] = (self._status[slot] or []) + [(words, [images[k[1]] for k in pg_keys], png)]
             self._upload_done(slot, stream)
         if dec_keys:
             rc = _lib.lib().io_rle_decode_u8(C.c_void_p(base + tab_at), C.c_size_t(ends.size), C.c_void_p(base + rd_at),
@@ -370,7 +397,7 @@ class _Batches(object):
                 seen[key] = len(masks)
                 masks.append(p["modal"])
                 img = self.load_image(p["image_fn"]) if load_rgb else None
-                images.append(img if img is None or is_jpeg(img) else np.asarray(img))
+                images.append(img if img is None or is_jpeg(img) or is_png(img) else np.asarray(img))
             items.append((seen[key], p["idx1"], p["idx2"], p["box"], p["interp"], p["flip"]))
         return self.renderer.render(images, masks, items, load_rgb=load_rgb)
 
@@ -547,7 +574,7 @@ class BatchPrefetcher(object):
                         self._q.put((out, ev))
                     renderer = getattr(self.batches, "_renderer", None)
                     if renderer is not None:
-                        renderer.check_status()        # a JPEG image of the last two batches that did not decode
+                        renderer.check_status()        # a JPEG or PNG image of the last two batches that did not decode
             except BaseException as e:          # surfaced on the consumer side
                 self._err = e
             self._q.put(None)

@@ -90,6 +90,17 @@ def _read_png16(path):
     return a.astype(np.uint16) if a.dtype != np.uint16 else a
 
 
+def _device_png(path, raw16):
+    """the file as a ``png.PngImage`` when the device decoder takes it in the wanted form (8-bit picture, or 16-bit
+    grayscale with ``raw16``), else None: the caller reads it on the host"""
+    from . import png
+    try:
+        im = png.PngImage.open(path)
+    except ValueError:
+        return None
+    return im if im.supported and im.raw16 == raw16 else None
+
+
 def kitti_crop_box(H, W):
     """datasets/reader.py:83-85: the bottom 352 rows, 1216 columns starting at int((W - 1216) / 2) -> (x, y, w, h)."""
     if H < KITTI_H or W < KITTI_W:
@@ -100,9 +111,18 @@ def kitti_crop_box(H, W):
 class KITTIEigenReader(object):
     """datasets/reader.py:69-96 KITTIDataset: list lines ``image depth [focal]``; images under ``<root>/rawdata/``, 16-bit
     ground truth under ``<root>/data_depth_annotated/``.  A ground truth that does not exist (the Eigen list names
-    ``None`` for some images) is reported by ``has_gt``."""
+    ``None`` for some images) is reported by ``has_gt``.  ``png="device"``: ``load`` returns the frame and the ground truth
+    as ``png.PngImage`` objects (the ground truth whole, in the raw16 form) for ``io_png_decode``; a file that is not in a
+    form the device decoder takes comes as the array of the default ``"host"`` path.  ``png=None`` (the default) takes the
+    environment variable IO_KITTI_PNG, "host" when it is unset or empty: the switch of ``tools/test_disp.py``, which builds
+    its reader without the argument.  Any other value, from either source, raises ValueError."""
 
-    def __init__(self, list_file, root, test_num=-1):
+    def __init__(self, list_file, root, test_num=-1, png=None):
+        if png is None:
+            png = os.environ.get("IO_KITTI_PNG", "") or "host"
+        if png not in ("host", "device"):
+            raise ValueError("KITTIEigenReader: png %r ('host' or 'device'; IO_KITTI_PNG when not given)" % (png,))
+        self.png = png
         with open(list_file, "r") as f:
             lines = [ln.split() for ln in f.readlines()]
         lines = [ln for ln in lines if ln]
@@ -118,9 +138,18 @@ class KITTIEigenReader(object):
         return os.path.isfile(self.depth_paths[i])
 
     def load(self, i):
-        """-> (uint8 image [H,W,3], crop box (x, y, w, h), raw uint16 ground truth cropped to [352,1216] or None)."""
-        img = _read_rgb(self.image_paths[i])
+        """-> (uint8 image [H,W,3], crop box (x, y, w, h), raw uint16 ground truth cropped to [352,1216] or None); with
+        ``png="device"`` the image and the (uncropped) ground truth may be ``png.PngImage`` objects."""
+        img = _device_png(self.image_paths[i], False) if self.png == "device" else None
+        if img is None:
+            img = _read_rgb(self.image_paths[i])
         box = kitti_crop_box(img.shape[0], img.shape[1])
+        gt = None
+        if self.png == "device" and os.path.isfile(self.depth_paths[i]):
+            gt = _device_png(self.depth_paths[i], True)
+            if gt is not None:
+                kitti_crop_box(gt.H, gt.W)
+                return img, box, gt
         gt = _read_png16(self.depth_paths[i])
         if gt is not None:
             x, y, w, h = kitti_crop_box(gt.shape[0], gt.shape[1])
@@ -277,6 +306,7 @@ def eval_dense_depth(model, reader, algo, batch=4, min_depth=1e-3, max_depth=80,
     missing = n - len(present)
     mine = [i for i in _shard(len(present), world_size, rank)]
     ren = _renderer((KITTI_H, KITTI_W), data_mean, data_std, dev)
+    from . import png
 
     def make(ks):
         imgs, boxes, gts = [], [], []
@@ -284,13 +314,25 @@ def eval_dense_depth(model, reader, algo, batch=4, min_depth=1e-3, max_depth=80,
             img, box, gt = reader.load(present[k])
             if gt is None:
                 raise RuntimeError("ground truth of %s disappeared" % reader.image_paths[present[k]])
-            if gt.shape != (KITTI_H, KITTI_W):
+            if not png.is_png(gt) and gt.shape != (KITTI_H, KITTI_W):
                 raise ValueError("ground truth %s: crop %s" % (reader.depth_paths[present[k]], gt.shape))
             imgs.append(img)
             boxes.append(box)
             gts.append(gt)
         rgb = render_rgb(ren, imgs, boxes)
-        g = torch.from_numpy(np.stack(gts).view(np.int16)).pin_memory().to(dev, non_blocking=True)
+        on_dev = [j for j, gt in enumerate(gts) if png.is_png(gt)]
+        if not on_dev:
+            g = torch.from_numpy(np.stack(gts).view(np.int16)).pin_memory().to(dev, non_blocking=True)
+            return (rgb, g), list(ks)
+        # ground truth that arrived as PNG files: one decode for the batch on this (the prefetch) stream, cropped on the device
+        g = torch.empty((len(gts), KITTI_H, KITTI_W), dtype=torch.int16, device=dev)
+        maps = png.decode([gts[j] for j in on_dev], dev)
+        for j, m in zip(on_dev, maps):
+            x, y, w, h = kitti_crop_box(m.shape[0], m.shape[1])
+            g[j].copy_(m.view(torch.int16)[y:y + h, x:x + w])
+        for j, gt in enumerate(gts):
+            if not png.is_png(gt):
+                g[j].copy_(torch.from_numpy(gt.view(np.int16)).pin_memory(), non_blocking=True)
         return (rgb, g), list(ks)
 
     chunks = []
@@ -301,6 +343,7 @@ def eval_dense_depth(model, reader, algo, batch=4, min_depth=1e-3, max_depth=80,
             chunks.append((ks, depth_errors_median(disp, g, 256.0, min_depth, max_depth)))
     finally:
         pf.close()
+    ren.check_status()                                       # a PNG frame of the last batches that did not decode
     table = _collect(chunks, len(present), world_size)
     out = {}
     means = table[:, :8].mean(0) if len(present) else np.full(8, np.nan)

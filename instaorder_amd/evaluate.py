@@ -163,9 +163,10 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
 
 
 def _loaded(image):
-    """a ``jpeg.JpegImage`` goes to the renderer as it is"""
+    """a ``jpeg.JpegImage`` or ``png.PngImage`` goes to the renderer as it is"""
     from .jpeg import is_jpeg
-    return image if is_jpeg(image) else np.asarray(image)
+    from .png import is_png
+    return image if is_jpeg(image) or is_png(image) else np.asarray(image)
 
 
 def _identity_inputs(image, modal, size):

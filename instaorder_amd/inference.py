@@ -310,22 +310,28 @@ def _host_masks(masks, mr):
 
 
 def _device_image(image):
-    """what the renderer takes: a ``jpeg.JpegImage`` as it is (decoded on the device), anything else as a uint8 array"""
+    """what the renderer takes: a ``jpeg.JpegImage`` or ``png.PngImage`` as it is (decoded on the device), anything else
+    as a uint8 array"""
     from .jpeg import is_jpeg
-    return image if is_jpeg(image) else np.ascontiguousarray(image.astype(np.uint8))
+    from .png import is_png
+    return image if is_jpeg(image) or is_png(image) else np.ascontiguousarray(image.astype(np.uint8))
 
 
 def host_image(image, dev):
-    """uint8 [H,W,3] on the host for the paths that need pixels there; a ``jpeg.JpegImage`` is decoded on the device"""
-    from . import jpeg
+    """uint8 [H,W,3] on the host for the paths that need pixels there; a ``jpeg.JpegImage`` or ``png.PngImage`` is
+    decoded on the device"""
+    from . import jpeg, png
+    if png.is_png(image):
+        return png.decode([image], dev)[0].cpu().numpy()
     return jpeg.decode([image], dev)[0].cpu().numpy() if jpeg.is_jpeg(image) else image
 
 
 def _render_checked(r, image, *args, **kw):
-    """render, and for a JPEG image wait for its status: a file that does not decode must not yield an order matrix"""
+    """render, and for a JPEG or PNG image wait for its status: a file that does not decode must not yield an order matrix"""
     from .jpeg import is_jpeg
+    from .png import is_png
     out = r.render([image], *args, **kw)
-    if is_jpeg(image):
+    if is_jpeg(image) or is_png(image):
         r.check_status()
     return out
 

@@ -1,0 +1,646 @@
+"""PNG images and 16-bit depth maps for the device input pipeline.
+
+KINS / KITTI frames are 8-bit RGB PNG files and the KITTI ground-truth depth maps 16-bit grayscale ones; the reference
+loads them with ``Image.open(fn).convert('RGB')`` (datasets/occ_order_dataset.py:79) and ``cv2.imread(f, -1)``.  A
+``PngImage`` keeps the file's bytes instead: the chunks are parsed here (pure Python, no GPU needed), only the DEFLATE
+stream and a descriptor are uploaded, and ``io_png_decode`` (csrc/png.hip) decodes in front of the render kernel
+(``datasets.PairRenderer``) or of the depth metrics (``dense_eval``), next to the JPEG images and the encoded masks.
+
+The rule (DESIGN.md "PNG images") is RFC 1950 / 1951 / 2083 with zlib's acceptance rules, all in integers:
+
+1. Inflate: the concatenated IDAT payloads are one zlib stream; its DEFLATE bytes must yield exactly ``H * (1 + rowbytes)``
+   bytes whose Adler-32 is the big-endian word at the end of the stream.
+2. Unfilter: every scanline starts with a filter byte 0..4 (None, Sub, Up, Average, Paeth), applied per byte with the
+   pixel to the left (``bpp`` bytes back), the byte above and the one above left, zero outside the image, modulo 256.
+3. Pack: 8-bit RGB is copied, RGBA loses its alpha, gray is replicated to R = G = B -- uint8 [H, W, 3], exactly
+   ``np.array(Image.open(f).convert('RGB'))``; 16-bit gray ("raw16") becomes uint16 [H, W] in host byte order, the
+   values ``cv2.imread(f, -1)`` gives, and is not a picture: the renderer refuses it.
+
+``PngImage.to_host()`` is that rule in NumPy and the contract of the kernels; ``PngImage.inflate_status()`` states the
+inflate stage of csrc/png_inflate.h in Python, status word by status word.
+"""
+import ctypes as C
+import os
+import struct
+import zlib
+
+import numpy as np
+
+from . import _lib
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+STATUS = {1: "block type 3", 2: "a stored block whose length and complement disagree", 3: "an invalid code-length set",
+          4: "an invalid literal/length or distance symbol", 5: "a distance reaching before the first output byte",
+          6: "data exhausted before the end of the final block", 7: "the stream does not yield H * (1 + rowbytes) bytes",
+          8: "Adler-32 mismatch", 9: "a filter byte above 4"}
+UNFILTER_BAND = 64           # PNG_BAND_ROWS of csrc/png.hip: rows the skewed wavefront of the unfilter stage takes at once
+
+_LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+_LEN_EXTRA = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
+_DIST_BASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097,
+              6145, 8193, 12289, 16385, 24577]
+_DIST_EXTRA = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
+_CL_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
+_REV = np.array([int("{:015b}".format(i)[::-1], 2) for i in range(1 << 15)], np.int64)
+
+
+class PngStreamError(ValueError):
+    """the zlib stream of a well-formed file does not decode; ``status`` is the kernel's status word"""
+
+    def __init__(self, status, name):
+        ValueError.__init__(self, "PNG image %s: %s (status %d)" % (name, STATUS.get(status, "?"), status))
+        self.status = status
+
+
+def _code_table(lengths, kind):
+    """15-bit lookup (index: the next 15 stream bits, first bit lowest) -> (length << 9) | symbol, 0 where no code starts,
+    by zlib's inflate_table rules; None for a set it refuses.  kind: "codes" (the code-length code: must be complete),
+    "lens" / "dists" (incomplete only as a single 1-bit code; "dists" may be empty)."""
+    lengths = np.asarray(lengths, np.int64)
+    count = np.bincount(lengths, minlength=16)
+    tab = np.zeros(1 << 15, np.int32)
+    if count[0] == lengths.size:
+        return None if kind == "codes" else tab              # no distance codes at all is no error by itself
+    left = 1
+    for l in range(1, 16):
+        left = (left << 1) - int(count[l])
+        if left < 0:
+            return None
+    longest = int(np.nonzero(count[1:])[0].max()) + 1
+    if left > 0 and (kind == "codes" or longest != 1):
+        return None
+    code = 0
+    nxt = [0] * 16
+    for l in range(1, 16):
+        code = (code + int(count[l - 1] if l > 1 else 0)) << 1
+        nxt[l] = code
+    for sym, l in enumerate(lengths):
+        l = int(l)
+        if l:
+            rev = int(_REV[nxt[l]]) >> (15 - l)
+            nxt[l] += 1
+            tab[rev::1 << l] = (l << 9) | sym
+    return tab
+
+
+_FIXED = []
+
+
+def _fixed_tables():
+    if not _FIXED:
+        _FIXED.append(_code_table([8] * 144 + [9] * 112 + [7] * 24 + [8] * 8, "lens"))
+        _FIXED.append(_code_table([5] * 32, "dists"))
+    return _FIXED
+
+
+def inflate_walk(data, expected=None, keep=True):
+    """The inflate loop of csrc/png_inflate.h in Python over raw DEFLATE bytes: (status, bytes produced or None, stats).
+    ``expected``: the byte count the stream must yield (status 7 otherwise; None: any).  stats: dict(stored, fixed,
+    dynamic, min_distance, max_distance, max_length, overlapping, max_code_length, output_bytes).  Slow: small files."""
+    data = bytes(data)
+    nb = len(data)
+    st = dict(stored=0, fixed=0, dynamic=0, min_distance=0, max_distance=0, max_length=0, overlapping=0,
+              max_code_length=0, output_bytes=0)
+    out = bytearray()
+    n_out = 0
+    buf, cnt, pos = 0, 0, 0
+
+    def done(status):
+        st["output_bytes"] = n_out
+        return status, (bytes(out) if keep and status == 0 else None), st
+
+    def over():
+        return 8 * pos - cnt > 8 * nb
+
+    while True:
+        while cnt < 3:
+            buf |= (data[pos] if pos < nb else 0) << cnt
+            pos += 1
+            cnt += 8
+        final, kind = buf & 1, (buf >> 1) & 3
+        buf >>= 3
+        cnt -= 3
+        if over():
+            return done(6)
+        if kind == 3:
+            return done(1)
+        if kind == 0:
+            buf >>= cnt & 7
+            cnt -= cnt & 7
+            while cnt < 32:
+                buf |= (data[pos] if pos < nb else 0) << cnt
+                pos += 1
+                cnt += 8
+            ln, nln = buf & 0xFFFF, (buf >> 16) & 0xFFFF
+            buf >>= 32
+            cnt -= 32
+            if over():
+                return done(6)
+            if ln != nln ^ 0xFFFF:
+                return done(2)
+            pos -= cnt >> 3
+            buf, cnt = 0, 0
+            if pos + ln > nb:
+                return done(6)
+            if expected is not None and n_out + ln > expected:
+                return done(7)
+            st["stored"] += 1
+            if keep:
+                out += data[pos:pos + ln]
+            n_out += ln
+            pos += ln
+        else:
+            if kind == 1:
+                st["fixed"] += 1
+                lit, dist = _fixed_tables()
+            else:
+                while cnt < 14:
+                    buf |= (data[pos] if pos < nb else 0) << cnt
+                    pos += 1
+                    cnt += 8
+                nlen, ndist, ncode = (buf & 31) + 257, ((buf >> 5) & 31) + 1, ((buf >> 10) & 15) + 4
+                buf >>= 14
+                cnt -= 14
+                if over():
+                    return done(6)
+                if nlen > 286 or ndist > 30:
+                    return done(3)
+                cl = [0] * 19
+                for i in range(ncode):
+                    while cnt < 3:
+                        buf |= (data[pos] if pos < nb else 0) << cnt
+                        pos += 1
+                        cnt += 8
+                    cl[_CL_ORDER[i]] = buf & 7
+                    buf >>= 3
+                    cnt -= 3
+                if over():
+                    return done(6)
+                ctab = _code_table(cl, "codes")
+                if ctab is None:
+                    return done(3)
+                lens = []
+                while len(lens) < nlen + ndist:
+                    while cnt < 22:
+                        buf |= (data[pos] if pos < nb else 0) << cnt
+                        pos += 1
+                        cnt += 8
+                    e = int(ctab[buf & 0x7FFF])
+                    l, sym = e >> 9, e & 511                             # the code is complete: every pattern decodes
+                    buf >>= l
+                    cnt -= l
+                    if sym < 16:
+                        if over():
+                            return done(6)
+                        lens.append(sym)
+                        continue
+                    if sym == 16:
+                        rep, val = 3 + (buf & 3), (lens[-1] if lens else -1)
+                        l = 2
+                    elif sym == 17:
+                        rep, val, l = 3 + (buf & 7), 0, 3
+                    else:
+                        rep, val, l = 11 + (buf & 127), 0, 7
+                    buf >>= l
+                    cnt -= l
+                    if over():
+                        return done(6)
+                    if val < 0 or len(lens) + rep > nlen + ndist:
+                        return done(3)
+                    lens += [val] * rep
+                if lens[256] == 0:
+                    return done(3)
+                lit = _code_table(lens[:nlen], "lens")
+                dist = _code_table(lens[nlen:], "dists") if lit is not None else None
+                if lit is None or dist is None:
+                    return done(3)
+                st["dynamic"] += 1
+            while True:
+                while cnt < 48:
+                    buf |= (data[pos] if pos < nb else 0) << cnt
+                    pos += 1
+                    cnt += 8
+                e = int(lit[buf & 0x7FFF])
+                if e == 0:
+                    return done(6 if 8 * nb - (8 * pos - cnt) < 15 else 4)     # a longer code might have followed
+                l, sym = e >> 9, e & 511
+                buf >>= l
+                cnt -= l
+                if over():
+                    return done(6)
+                if l > st["max_code_length"]:
+                    st["max_code_length"] = l
+                if sym < 256:
+                    if expected is not None and n_out >= expected:
+                        return done(7)
+                    if keep:
+                        out.append(sym)
+                    n_out += 1
+                    continue
+                if sym == 256:
+                    break
+                if sym > 285:
+                    return done(4)
+                ln = _LEN_BASE[sym - 257] + (buf & ((1 << _LEN_EXTRA[sym - 257]) - 1))
+                buf >>= _LEN_EXTRA[sym - 257]
+                cnt -= _LEN_EXTRA[sym - 257]
+                e = int(dist[buf & 0x7FFF])
+                if e == 0:
+                    return done(6 if 8 * nb - (8 * pos - cnt) < 15 else 4)     # a longer code might have followed
+                l, ds = e >> 9, e & 511
+                buf >>= l
+                cnt -= l
+                if over():
+                    return done(6)
+                if l > st["max_code_length"]:
+                    st["max_code_length"] = l
+                if ds > 29:
+                    return done(4)
+                d = _DIST_BASE[ds] + (buf & ((1 << _DIST_EXTRA[ds]) - 1))
+                buf >>= _DIST_EXTRA[ds]
+                cnt -= _DIST_EXTRA[ds]
+                if over():
+                    return done(6)
+                if d > n_out:
+                    return done(5)
+                if expected is not None and n_out + ln > expected:
+                    return done(7)
+                st["min_distance"] = d if st["min_distance"] == 0 else min(st["min_distance"], d)
+                st["max_distance"] = max(st["max_distance"], d)
+                st["max_length"] = max(st["max_length"], ln)
+                st["overlapping"] += d < ln
+                if keep:
+                    if d >= ln:
+                        out += out[n_out - d:n_out - d + ln]
+                    else:
+                        seg = bytes(out[n_out - d:])
+                        out += (seg * (ln // d + 1))[:ln]
+                n_out += ln
+        if final:
+            break
+    if expected is not None and n_out != expected:
+        return done(7)
+    return done(0)
+
+
+def _unfilter(raw, H, rowbytes, bpp):
+    """stage 2 on the inflated bytes (uint8 [H * (1 + rowbytes)]) -> uint8 [H, rowbytes]; None when a filter byte is above
+    4.  One NumPy step per anti-diagonal of pixels: the skewed wavefront of the kernel."""
+    rows = raw.reshape(H, 1 + rowbytes)
+    ft = rows[:, 0].astype(np.int64)
+    if ft.size and ft.max() > 4:
+        return None
+    W = rowbytes // bpp
+    src = rows[:, 1:].reshape(H, W, bpp).astype(np.int32)
+    if not np.any(ft > 2):                                   # None / Sub / Up only: whole rows at a time
+        out = np.zeros((H + 1, W, bpp), np.int32)
+        for y in range(H):
+            if ft[y] == 1:
+                out[y + 1] = np.cumsum(src[y], axis=0) & 255
+            elif ft[y] == 2:
+                out[y + 1] = (src[y] + out[y]) & 255
+            else:
+                out[y + 1] = src[y]
+        return out[1:].astype(np.uint8).reshape(H, rowbytes)
+    out = np.zeros((H + 1, W + 1, bpp), np.int32)            # a zero row above and a zero column to the left
+    ftc = ft[:, None]
+    for s in range(H + W - 1):
+        ys = np.arange(max(0, s - W + 1), min(H, s + 1))
+        xs = s - ys
+        a, b, c = out[ys + 1, xs], out[ys, xs + 1], out[ys, xs]
+        p = a + b - c
+        pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
+        paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+        t = ftc[ys]
+        pred = np.where(t == 1, a, np.where(t == 2, b, np.where(t == 3, (a + b) >> 1, np.where(t == 4, paeth, 0))))
+        out[ys + 1, xs + 1] = (src[ys, xs] + pred) & 255
+    return out[1:, 1:].astype(np.uint8).reshape(H, rowbytes)
+
+
+class PngImage(object):
+    """One PNG file, parsed but not decoded.  Stands in for a uint8 [H, W, 3] array (a uint16 [H, W] one in the raw16
+    form) where the consumers only look at ``shape`` / ``dtype``; ``supported`` says whether the device decoder takes it
+    (``reason`` why not)."""
+
+    def __init__(self, data, name=None):
+        self.data = bytes(data)
+        self.name = name if name is not None else "<%d bytes>" % len(self.data)
+        self.reason = None
+        self.H = self.W = 0
+        self.bit_depth = self.colour_type = self.interlace = 0
+        self.channels = 0                # samples per pixel in the file
+        self.chunks = []                 # (type, payload length) in file order
+        self.adler = 0
+        self.nbytes_stream = 0           # the zlib stream: header, DEFLATE bytes, Adler-32
+        self._deflate = b""
+        self._parse()
+
+    @classmethod
+    def open(cls, path):
+        with open(path, "rb") as f:
+            return cls(f.read(), name=str(path))
+
+    # ---- the array surface -------------------------------------------------------------------------------------------
+    @property
+    def raw16(self):
+        return self.colour_type == 0 and self.bit_depth == 16
+
+    @property
+    def shape(self):
+        return (self.H, self.W) if self.raw16 else (self.H, self.W, 3)
+
+    @property
+    def ndim(self):
+        return 2 if self.raw16 else 3
+
+    @property
+    def dtype(self):
+        return np.dtype(np.uint16 if self.raw16 else np.uint8)
+
+    @property
+    def supported(self):
+        return self.reason is None
+
+    @property
+    def nbytes_compressed(self):
+        return len(self.data)
+
+    @property
+    def bpp(self):
+        """bytes per pixel in the file: the distance of the Sub / Average / Paeth filters"""
+        return max(1, self.channels * self.bit_depth // 8)
+
+    @property
+    def rowbytes(self):
+        return (self.W * self.channels * self.bit_depth + 7) // 8
+
+    @property
+    def inflated_bytes(self):
+        return self.H * (1 + self.rowbytes)
+
+    @property
+    def out_bytes(self):
+        return self.H * self.W * (2 if self.raw16 else 3)
+
+    def _no(self, reason):
+        if self.reason is None:
+            self.reason = reason
+
+    # ---- chunks ------------------------------------------------------------------------------------------------------
+    def _parse(self):
+        b = self.data
+        n = len(b)
+        if b[:8] != SIGNATURE:
+            raise ValueError("PNG %s: no PNG signature" % self.name)
+        p = 8
+        idat = []
+        seen_ihdr = False
+        while p < n:
+            if p + 12 > n:
+                raise ValueError("PNG %s: the file ends inside a chunk header (byte %d)" % (self.name, p))
+            L, ctype = struct.unpack_from(">I4s", b, p)
+            if p + 12 + L > n:
+                raise ValueError("PNG %s: chunk %r of length %d runs past the end of the file" % (self.name, ctype, L))
+            body = b[p + 8:p + 8 + L]
+            crc = struct.unpack_from(">I", b, p + 8 + L)[0]
+            p += 12 + L
+            if not seen_ihdr and ctype != b"IHDR":
+                raise ValueError("PNG %s: the first chunk is %r, not IHDR" % (self.name, ctype))
+            if ctype in (b"IHDR", b"IDAT") and zlib.crc32(ctype + body) & 0xFFFFFFFF != crc:
+                raise ValueError("PNG %s: bad CRC of an %s chunk" % (self.name, ctype.decode()))
+            self.chunks.append((ctype.decode("latin-1"), L))
+            if ctype == b"IHDR":
+                if seen_ihdr or L != 13:
+                    raise ValueError("PNG %s: malformed IHDR" % self.name)
+                seen_ihdr = True
+                self.W, self.H, self.bit_depth, self.colour_type, comp, filt, self.interlace = struct.unpack(">IIBBBBB", body)
+            elif ctype == b"IDAT":
+                idat.append(body)
+            elif ctype == b"IEND":
+                break
+        if not seen_ihdr or not idat:
+            raise ValueError("PNG %s: no IHDR or no IDAT chunk" % self.name)
+        if self.W == 0 or self.H == 0 or comp != 0 or filt != 0 or self.interlace > 1:
+            raise ValueError("PNG %s: invalid IHDR (%d x %d, compression %d, filter %d, interlace %d)"
+                             % (self.name, self.W, self.H, comp, filt, self.interlace))
+        self.channels = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}.get(self.colour_type, 0)
+        if self.channels == 0 or self.bit_depth not in (1, 2, 4, 8, 16):
+            raise ValueError("PNG %s: colour type %d with bit depth %d" % (self.name, self.colour_type, self.bit_depth))
+        stream = b"".join(idat)
+        self.nbytes_stream = len(stream)
+        if len(stream) < 6:
+            raise ValueError("PNG %s: a zlib stream of %d bytes" % (self.name, len(stream)))
+        cmf, flg = stream[0], stream[1]
+        if cmf & 15 != 8 or cmf >> 4 > 7 or flg & 0x20 or (cmf * 256 + flg) % 31:
+            raise ValueError("PNG %s: invalid zlib header %02x %02x" % (self.name, cmf, flg))
+        self._deflate = stream[2:-4]
+        self.adler = struct.unpack(">I", stream[-4:])[0]
+        if self.interlace:
+            self._no("Adam7 interlace")
+        elif self.colour_type == 3:
+            self._no("palette colour")
+        elif self.bit_depth < 8:
+            self._no("%d-bit samples" % self.bit_depth)
+        elif self.bit_depth == 16 and self.colour_type != 0:
+            self._no("16-bit colour")
+        elif self.colour_type == 4:
+            self._no("gray with alpha")
+        if self.H > 65535 or self.W > 65535:
+            self._no("size %d x %d above 65535" % (self.H, self.W))
+        elif 3 * self.H * self.W >= 1 << 31:
+            self._no("3 H W = %d is 2^31 or more" % (3 * self.H * self.W))
+
+    def _require(self):
+        if not self.supported:
+            raise ValueError("PNG image %s is not supported by the device decoder: %s" % (self.name, self.reason))
+
+    # ---- what the device reads ---------------------------------------------------------------------------------------
+    def deflate_bytes(self):
+        """the DEFLATE bytes: the zlib stream without its two header bytes and its Adler-32"""
+        return self._deflate
+
+    def with_stream(self, deflate, adler=None, name=None):
+        """the same header over other DEFLATE bytes (and Adler-32 word), taken as they are: how tests and tools build
+        truncated or damaged streams"""
+        import copy
+        out = copy.copy(self)
+        out._deflate = bytes(deflate)
+        if adler is not None:
+            out.adler = int(adler) & 0xFFFFFFFF
+        out.name = name if name is not None else self.name + " (altered)"
+        return out
+
+    # ---- the rule in Python / NumPy ----------------------------------------------------------------------------------
+    def stream_stats(self):
+        """What the DEFLATE stream is made of, by a pure-Python walk (slow; for small files and tests): dict(stored,
+        fixed, dynamic: blocks of each type; min_distance, max_distance, max_length: of the matches, 0 without one;
+        overlapping: matches with distance < length; max_code_length: the longest Huffman code used; output_bytes;
+        status: the status word of the walk, without the size, checksum and filter checks)."""
+        status, _, st = inflate_walk(self._deflate, None, keep=False)
+        st["status"] = status
+        return st
+
+    def inflate_status(self):
+        """(status word of stage 1 with its Adler-32 check, the inflated bytes or None): csrc/png_inflate.h in Python"""
+        status, out, _ = inflate_walk(self._deflate, self.inflated_bytes)
+        if status == 0 and zlib.adler32(out) & 0xFFFFFFFF != self.adler:
+            return 8, None
+        return status, out
+
+    def _inflate(self):
+        d = zlib.decompressobj(-15)
+        try:
+            out = d.decompress(self._deflate, self.inflated_bytes + 1)
+        except zlib.error:
+            out = None
+        if out is None or not d.eof or len(out) != self.inflated_bytes or zlib.adler32(out) & 0xFFFFFFFF != self.adler:
+            status = self.inflate_status()[0]
+            raise PngStreamError(status if status else 7, self.name)
+        return np.frombuffer(out, np.uint8)
+
+    def to_host(self):
+        """uint8 [H, W, 3] (uint16 [H, W] in the raw16 form) by the rule of the module docstring: the contract of the
+        kernels.  PngStreamError with the kernel's status word for a stream that does not decode."""
+        self._require()
+        raw = self._inflate()
+        px = _unfilter(raw, self.H, self.rowbytes, self.bpp)
+        if px is None:
+            raise PngStreamError(9, self.name)
+        H, W = self.H, self.W
+        if self.raw16:
+            return px.reshape(H, W, 2).view(">u2").reshape(H, W).astype(np.uint16)
+        if self.channels == 1:
+            return np.repeat(px.reshape(H, W, 1), 3, axis=2)
+        return np.ascontiguousarray(px.reshape(H, W, self.channels)[:, :, :3])
+
+
+def is_png(x):
+    return isinstance(x, PngImage)
+
+
+# ---- device side -------------------------------------------------------------------------------------------------------
+def descriptors(images, out_offs):
+    """(pool uint8, PngDesc array) for a list of supported ``PngImage`` and the byte offset of each decoded image: what
+    ``io_png_decode`` reads"""
+    desc = (_lib.PngDesc * len(images))()
+    chunks, cursor = [], 0
+    for k, (im, o) in enumerate(zip(images, out_offs)):
+        im._require()
+        d = desc[k]
+        data = im.deflate_bytes()
+        d.data_off, d.data_bytes, d.out_off = cursor, len(data), int(o)
+        d.H, d.W, d.channels, d.depth, d.adler = im.H, im.W, im.channels, im.bit_depth, im.adler
+        chunks.append(data)
+        cursor += len(data)
+    pool = np.frombuffer(b"".join(chunks), np.uint8) if cursor else np.zeros(0, np.uint8)
+    return pool, desc
+
+
+def workspace_bytes(desc):
+    b = int(_lib.lib().io_png_workspace_bytes(C.cast(desc, C.c_void_p), len(desc)))
+    if b == 0:
+        raise RuntimeError("instaorder_hip io_png_workspace_bytes refused the descriptors: %s" % _lib.last_error())
+    return b
+
+
+def launch(pool, pool_bytes, desc_dev, desc, out, out_bytes, ws, ws_bytes, status, stream):
+    """one ``io_png_decode`` call.  Device addresses as ints; ``desc``: the host PngDesc array."""
+    rc = _lib.lib().io_png_decode(C.c_void_p(pool), C.c_size_t(pool_bytes), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p),
+                                  len(desc), C.c_void_p(out), C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes),
+                                  C.c_void_p(status), C.c_void_p(stream))
+    _lib.check(rc, "io_png_decode")
+
+
+def raise_for_status(status, images):
+    """RuntimeError naming the images whose status word is not zero"""
+    bad = [(im.name, int(s)) for im, s in zip(images, status) if int(s) != 0]
+    if bad:
+        raise RuntimeError("PNG decode failed: " + "; ".join("%s: %s (status %d)" % (nm, STATUS.get(s, "?"), s)
+                                                              for nm, s in bad))
+
+
+def decode(images, device, out=None, check=True):
+    """list of supported ``PngImage`` -> list of device tensors, uint8 [H, W, 3] or uint16 [H, W] (raw16), through one
+    ``io_png_decode`` call on the current stream: views of ``out``, a contiguous uint8 device tensor of at least the
+    summed sizes (each rounded up to 16 bytes), when given.  Waits for the status words and raises RuntimeError naming
+    the images that did not decode; with ``check=False`` it does not wait and returns (tensors, status tensor, images)
+    for ``raise_for_status`` later.  A uint16 result may be viewed as int16 storage (``t.view(torch.int16)``), which is
+    how ``ext_ops.depth_errors_median`` takes its ground truth."""
+    import torch
+    _lib.require_gpu()
+    device = torch.device(device)
+    images = list(images)
+    if not images:
+        return [] if check else ([], None, [])
+    for im in images:
+        if not is_png(im):
+            raise TypeError("png.decode takes PngImage objects (got %s)" % type(im).__name__)
+        im._require()
+    sizes = [im.out_bytes for im in images]
+    offs = [0]
+    for s in sizes[:-1]:
+        offs.append(offs[-1] + (s + 15) // 16 * 16)
+    total = offs[-1] + sizes[-1]
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < total:
+        raise ValueError("png.decode: out must be a contiguous uint8 device tensor of at least %d bytes" % total)
+    out = out.view(-1)
+    pool, desc = descriptors(images, offs)
+    dbytes = C.sizeof(desc)
+    host = np.zeros(dbytes + max(pool.size, 16), np.uint8)
+    host[:dbytes] = np.frombuffer(desc, dtype=np.uint8)
+    host[dbytes:dbytes + pool.size] = pool
+    dev = torch.from_numpy(host).to(out.device)
+    ws = torch.empty(workspace_bytes(desc), dtype=torch.uint8, device=out.device)
+    status = torch.empty(len(images), dtype=torch.int32, device=out.device)
+    base = dev.data_ptr()
+    launch(base + dbytes, pool.size, base, desc, out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel(),
+           status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream)
+    ws.record_stream(torch.cuda.current_stream(out.device))
+    dev.record_stream(torch.cuda.current_stream(out.device))
+    res = []
+    for o, s, im in zip(offs, sizes, images):
+        t = out[o:o + s]
+        res.append(t.view(torch.uint16).view(im.H, im.W) if im.raw16 else t.view(im.H, im.W, 3))
+    if not check:
+        return res, status, images
+    raise_for_status(status.cpu().numpy(), images)
+    return res
+
+
+def _pil_rgb(path):
+    try:
+        from PIL import Image
+    except ImportError:
+        raise RuntimeError("png.loader: %s is not a file the device decoders take and the default fallback needs "
+                           "Pillow, which is not installed; pass fallback=" % path)
+    return np.array(Image.open(path).convert("RGB"))
+
+
+def loader(image_root, jpeg=True, fallback=None):
+    """``load_image(image_fn)`` for the dataset classes: a ``PngImage`` for a PNG file in a supported 8-bit form, with
+    ``jpeg`` a ``jpeg.JpegImage`` for a baseline JPEG file the device decodes, otherwise ``fallback(path)`` -- by default
+    the reference's own ``np.array(Image.open(path).convert('RGB'))``."""
+    fallback = _pil_rgb if fallback is None else fallback
+
+    def load_image(image_fn):
+        path = os.path.join(image_root, image_fn)
+        with open(path, "rb") as f:
+            data = f.read()
+        im = None
+        try:
+            if data[:8] == SIGNATURE:
+                im = PngImage(data, name=str(image_fn))
+                if im.raw16:
+                    im = None
+            elif jpeg and data[:2] == b"\xff\xd8":
+                from .jpeg import JpegImage
+                im = JpegImage(data, name=str(image_fn))
+        except ValueError:
+            im = None
+        if im is not None and im.supported:
+            return im
+        return fallback(path)
+
+    return load_image
