@@ -842,6 +842,27 @@ int io_png_decode(const uint8_t* pool_dev, size_t pool_bytes, const io_png_desc*
                   hipStream_t stream);
 int io_png_band_rows(void);   /* rows per band of the unfilter stage in the built library */
 
+/* Parallel inflate (opt-in; csrc/png_inflate_par.h, DESIGN.md "Parallel inflate"): io_png_decode with stage (1) of ONE
+ * stream spread over many waves.  The DEFLATE bytes are cut into chunks of chunk_bytes (a multiple of 256 from 256 to
+ * 2^20, at most 65535 chunks per image); chunk 0 starts at bit 0 and every other chunk at the first bit of its range at
+ * which a complete dynamic-block header parses; every chunk decodes from there, block after block, up to a final block or
+ * to a block boundary that is exactly a later chunk's start, and counts; one lane per image chains the counts into output
+ * offsets; the chain chunks of a CLEAN image (no status on the chain, no reach in front of the first byte, a final exit,
+ * H (1 + rowbytes) bytes) decode again into 16-bit symbols, which two more launches turn into bytes.  Every other image
+ * -- damaged, one chain chunk, no data -- is decoded by the sequential stage behind them, under a per-image predicate
+ * and without a host wait, so outputs and status words are those of io_png_decode for every input.
+ *   info_dev (int32 per image, may be NULL): bits 0..15 the chunks on the chain (saturated), bit 16 not clean, bit 17
+ * clean but a chain of one; a value of 65536 or more means that the sequential kernel decoded the image.
+ *   Refused before anything is enqueued: all that io_png_decode refuses, a chunk_bytes outside the rule above, an image
+ * with more than 65535 chunks (IO_ERR_SHAPE), a workspace below io_png_par_workspace_bytes() (IO_ERR_WORKSPACE).
+ *   Workspace: io_png_workspace_bytes() + 32 units + round16(8 (n + 1)) + round16(8 n) + 48 chunks, where units is the sum
+ * over the images of ceil(H (1 + rowbytes) / 16), chunks the sum of ceil(data_bytes / chunk_bytes) and round16 rounds up
+ * to a multiple of 16.  Nothing is kept between calls. */
+size_t io_png_par_workspace_bytes(const io_png_desc* desc_host, int n, int chunk_bytes);   /* 0: refused */
+int io_png_decode_par(const uint8_t* pool_dev, size_t pool_bytes, const io_png_desc* desc_dev, const io_png_desc* desc_host,
+                      int n, uint8_t* out, size_t out_bytes, void* workspace, size_t workspace_bytes, int32_t* status_dev,
+                      int chunk_bytes, int32_t* info_dev, hipStream_t stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of every launch, per kernel class, on the launch
  * stream.  Process-global; io_prof_end synchronises on the recorded events and returns the number of
  * classes written.  flops / bytes are the ALGORITHMIC figures of the timed launches (the direct convolution's count). */

@@ -151,6 +151,9 @@ SIGNATURES = {
     "io_png_decode": (_I, [_P, _Z, _P, _P, _I, _P, _Z, _P, _Z, _P, _P]),
     "io_png_workspace_bytes": (_Z, [_P, _I]),
     "io_png_band_rows": (_I, []),
+    # the arguments of io_png_decode up to status_dev, then chunk_bytes, info_dev, stream
+    "io_png_decode_par": (_I, [_P, _Z, _P, _P, _I, _P, _Z, _P, _Z, _P, _I, _P, _P]),
+    "io_png_par_workspace_bytes": (_Z, [_P, _I, _I]),
     "io_order_loss": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _F, _F, _F, _P, _P, _P]),
     "io_sgd_momentum": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P]),
     # params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, stream

@@ -283,7 +283,8 @@ class PairRenderer(object):
         st_at = jws_at + jws_bytes
         end = st_at + 4 * len(jp_keys) if jp_keys else (ws_at + ws_bytes if pol_keys else nbytes)
         gws_at = (end + 15) // 16 * 16
-        gws_bytes = png.workspace_bytes(gdesc) if pg_keys else 0
+        ginf = png.get_inflate()                                     # as above: the stage png.set_inflate names
+        gws_bytes = png.workspace_bytes(gdesc, ginf) if pg_keys else 0
         gst_at = gws_at + gws_bytes
         if pg_keys:
             end = gst_at + 4 * len(pg_keys)
@@ -328,7 +329,7 @@ class PairRenderer(object):
             self._upload_done(slot, stream)
         if pg_keys:
             png.launch(base + gp_at, gpool.size, base + gd_at, gdesc, base, nbytes, base + gws_at, gws_bytes, base + gst_at,
-                       stream.cuda_stream)
+                       stream.cuda_stream, ginf)
             words = torch.empty(len(pg_keys), dtype=torch.int32).pin_memory()
             words.copy_(dev[gst_at:gst_at + 4 * len(pg_keys)].view(torch.int32), non_blocking=True)
             self._status[slot] = (self._status[slot] or []) + [(words, [images[k[1]] for k in pg_keys], png)]

@@ -18,6 +18,10 @@ The rule (DESIGN.md "PNG images") is RFC 1950 / 1951 / 2083 with zlib's acceptan
 
 ``PngImage.to_host()`` is that rule in NumPy and the contract of the kernels; ``PngImage.inflate_status()`` states the
 inflate stage of csrc/png_inflate.h in Python, status word by status word.
+
+The inflate stage runs in two ways with the same bytes and status words: one wave per image (``io_png_decode``) and one
+stream on many waves from found block starts (``io_png_decode_par``, csrc/png_inflate_par.h), chosen by ``set_inflate``;
+``PngImage.parallel_plan`` is the rule of the latter in Python.
 """
 import ctypes as C
 import os
@@ -93,10 +97,11 @@ def _fixed_tables():
     return _FIXED
 
 
-def inflate_walk(data, expected=None, keep=True):
+def inflate_walk(data, expected=None, keep=True, boundaries=None):
     """The inflate loop of csrc/png_inflate.h in Python over raw DEFLATE bytes: (status, bytes produced or None, stats).
     ``expected``: the byte count the stream must yield (status 7 otherwise; None: any).  stats: dict(stored, fixed,
-    dynamic, min_distance, max_distance, max_length, overlapping, max_code_length, output_bytes).  Slow: small files."""
+    dynamic, min_distance, max_distance, max_length, overlapping, max_code_length, output_bytes).  ``boundaries``: a list
+    that receives (bit, bytes produced so far) behind every block.  Slow: small files."""
     data = bytes(data)
     nb = len(data)
     st = dict(stored=0, fixed=0, dynamic=0, min_distance=0, max_distance=0, max_length=0, overlapping=0,
@@ -276,11 +281,256 @@ def inflate_walk(data, expected=None, keep=True):
                         seg = bytes(out[n_out - d:])
                         out += (seg * (ln // d + 1))[:ln]
                 n_out += ln
+        if boundaries is not None:
+            boundaries.append((8 * pos - cnt, n_out))
         if final:
             break
     if expected is not None and n_out != expected:
         return done(7)
     return done(0)
+
+
+# ---- parallel inflate: the rule of csrc/png_inflate_par.h ---------------------------------------------------------------
+PAR_MIN_CHUNK, PAR_MAX_CHUNK, PAR_MAX_CHUNKS = 256, 1 << 20, 65535
+INFO_NOT_CLEAN, INFO_CHAIN_OF_ONE = 1 << 16, 1 << 17
+EXIT_NONE, EXIT_FINAL, EXIT_LINK, EXIT_STATUS = 0, 1, 2, 3
+
+
+def _dynamic_header(data, bit):
+    """A dynamic-block header at ``bit`` (its BFINAL bit) by the rules of ``inflate_walk``: (literal/length table, distance
+    table, the bit behind the header), or the status word."""
+    nb = len(data)
+    pos = bit >> 3
+    buf, cnt = 0, 0
+
+    def need(n):
+        nonlocal buf, cnt, pos
+        while cnt < n:
+            buf |= (data[pos] if pos < nb else 0) << cnt
+            pos += 1
+            cnt += 8
+
+    def take(n):
+        nonlocal buf, cnt
+        v = buf & ((1 << n) - 1)
+        buf >>= n
+        cnt -= n
+        return v
+
+    def over():
+        return 8 * pos - cnt > 8 * nb
+
+    need(8)
+    take(bit & 7)
+    need(17)
+    take(1)
+    if take(2) != 2:
+        return 1
+    nlen, ndist, ncode = take(5) + 257, take(5) + 1, take(4) + 4
+    if over():
+        return 6
+    if nlen > 286 or ndist > 30:
+        return 3
+    cl = [0] * 19
+    for i in range(ncode):
+        need(3)
+        cl[_CL_ORDER[i]] = take(3)
+    if over():
+        return 6
+    ctab = _code_table(cl, "codes")
+    if ctab is None:
+        return 3
+    lens = []
+    while len(lens) < nlen + ndist:
+        need(22)
+        e = int(ctab[buf & 0x7FFF])
+        take(e >> 9)
+        sym = e & 511
+        if sym < 16:
+            rep, val = 1, sym
+        elif sym == 16:
+            rep, val = 3 + take(2), (lens[-1] if lens else -1)
+        elif sym == 17:
+            rep, val = 3 + take(3), 0
+        else:
+            rep, val = 11 + take(7), 0
+        if over():
+            return 6
+        if val < 0 or len(lens) + rep > nlen + ndist:
+            return 3
+        lens += [val] * rep
+    if lens[256] == 0:
+        return 3
+    lit = _code_table(lens[:nlen], "lens")
+    dist = _code_table(lens[nlen:], "dists") if lit is not None else None
+    if lit is None or dist is None:
+        return 3
+    return lit, dist, 8 * pos - cnt
+
+
+def dynamic_header_bits(data):
+    """every bit of ``data`` at which a complete dynamic-block header parses (search of csrc/png_inflate_par.h), ascending.
+    A vectorised necessary condition first -- BTYPE 2, HLIT <= 286, HDIST <= 30, a code-length code with Kraft sum 1 --
+    then the parse itself."""
+    data = bytes(data)
+    nb = len(data)
+    if nb == 0:
+        return []
+    bits = np.unpackbits(np.frombuffer(data, np.uint8), bitorder="little")
+    bits = np.concatenate([bits, np.zeros(96, np.uint8)]).astype(np.int64)
+    p = np.nonzero((bits[1:8 * nb + 1] == 0) & (bits[2:8 * nb + 2] == 1))[0]
+
+    def field(at, n):
+        v = np.zeros(p.size, np.int64)
+        for i in range(n):
+            v |= bits[p + at + i] << i
+        return v
+
+    keep = (field(3, 5) <= 29) & (field(8, 5) <= 29)
+    p = p[keep]
+    ncode = field(13, 4) + 4
+    kraft = np.zeros(p.size, np.int64)
+    for i in range(19):
+        v = field(17 + 3 * i, 3)
+        kraft += np.where((i < ncode) & (v > 0), 128 >> v, 0)
+    return [int(q) for q in p[kraft == 128] if not isinstance(_dynamic_header(data, int(q)), int)]
+
+
+def _chunk_walk(data, start, expected, cands, chunk_bits):
+    """One chunk's decode from bit ``start`` (count and store pass of csrc/png_inflate_par.h at once): dict(exit, exit_bit,
+    n, reach, status, next, syms: the 16-bit symbols as a list, blocks: [stored, fixed, dynamic], copied: markers that a
+    match copied from inside the chunk).  cands: {candidate bit: chunk}."""
+    nb = len(data)
+    pos = start >> 3
+    buf, cnt = 0, 0
+    while cnt < 8:
+        buf |= (data[pos] if pos < nb else 0) << cnt
+        pos += 1
+        cnt += 8
+    buf >>= start & 7
+    cnt -= start & 7
+    syms = []
+    blocks = [0, 0, 0]
+    rec = dict(exit=EXIT_NONE, exit_bit=0, n=0, reach=0, status=0, next=-1, syms=syms, blocks=blocks, copied=0)
+
+    def end(kind, status=0):
+        rec.update(exit=kind, status=status, exit_bit=8 * pos - cnt, n=len(syms))
+        return rec
+
+    while True:
+        while cnt < 3:
+            buf |= (data[pos] if pos < nb else 0) << cnt
+            pos += 1
+            cnt += 8
+        final, kind = buf & 1, (buf >> 1) & 3
+        buf >>= 3
+        cnt -= 3
+        if 8 * pos - cnt > 8 * nb:
+            return end(EXIT_STATUS, 6)
+        if kind == 3:
+            return end(EXIT_STATUS, 1)
+        if kind == 0:
+            buf >>= cnt & 7
+            cnt -= cnt & 7
+            while cnt < 32:
+                buf |= (data[pos] if pos < nb else 0) << cnt
+                pos += 1
+                cnt += 8
+            ln, nln = buf & 0xFFFF, (buf >> 16) & 0xFFFF
+            buf >>= 32
+            cnt -= 32
+            if 8 * pos - cnt > 8 * nb:
+                return end(EXIT_STATUS, 6)
+            if ln != nln ^ 0xFFFF:
+                return end(EXIT_STATUS, 2)
+            pos -= cnt >> 3
+            buf, cnt = 0, 0
+            if pos + ln > nb:
+                return end(EXIT_STATUS, 6)
+            if len(syms) + ln > expected:
+                return end(EXIT_STATUS, 7)
+            syms += data[pos:pos + ln]
+            pos += ln
+            blocks[0] += 1
+        else:
+            if kind == 1:
+                lit, dist = _fixed_tables()
+            else:
+                h = _dynamic_header(data, 8 * pos - cnt - 3)
+                if isinstance(h, int):
+                    return end(EXIT_STATUS, h)               # (exit_bit is the contract of "final" and "link" exits only)
+                lit, dist, at = h
+                pos, buf, cnt = at >> 3, 0, 0
+                while cnt < 8:
+                    buf |= (data[pos] if pos < nb else 0) << cnt
+                    pos += 1
+                    cnt += 8
+                buf >>= at & 7
+                cnt -= at & 7
+            blocks[kind] += 1
+            while True:
+                while cnt < 48:
+                    buf |= (data[pos] if pos < nb else 0) << cnt
+                    pos += 1
+                    cnt += 8
+                e = int(lit[buf & 0x7FFF])
+                if e == 0:
+                    return end(EXIT_STATUS, 6 if 8 * nb - (8 * pos - cnt) < 15 else 4)
+                l, sym = e >> 9, e & 511
+                buf >>= l
+                cnt -= l
+                if 8 * pos - cnt > 8 * nb:
+                    return end(EXIT_STATUS, 6)
+                if sym < 256:
+                    if len(syms) >= expected:
+                        return end(EXIT_STATUS, 7)
+                    syms.append(sym)
+                    continue
+                if sym == 256:
+                    break
+                if sym > 285:
+                    return end(EXIT_STATUS, 4)
+                x = _LEN_EXTRA[sym - 257]
+                ln = _LEN_BASE[sym - 257] + (buf & ((1 << x) - 1))
+                buf >>= x
+                cnt -= x
+                e = int(dist[buf & 0x7FFF])
+                if e == 0:
+                    return end(EXIT_STATUS, 6 if 8 * nb - (8 * pos - cnt) < 15 else 4)
+                l, ds = e >> 9, e & 511
+                buf >>= l
+                cnt -= l
+                if 8 * pos - cnt > 8 * nb:
+                    return end(EXIT_STATUS, 6)
+                if ds > 29:
+                    return end(EXIT_STATUS, 4)
+                x = _DIST_EXTRA[ds]
+                d = _DIST_BASE[ds] + (buf & ((1 << x) - 1))
+                buf >>= x
+                cnt -= x
+                if 8 * pos - cnt > 8 * nb:
+                    return end(EXIT_STATUS, 6)
+                n_out = len(syms)
+                if d > n_out:
+                    rec["reach"] = max(rec["reach"], d - n_out)
+                if n_out + ln > expected:
+                    return end(EXIT_STATUS, 7)
+                first = []                                   # the match's first min(d, ln) symbols
+                for k in range(min(d, ln)):
+                    src = n_out - d + k
+                    if src < 0:
+                        first.append(0x8000 | (-src - 1))
+                    else:
+                        first.append(syms[src])
+                        rec["copied"] += syms[src] >= 0x8000
+                syms += (first * (ln // len(first) + 1))[:ln]
+        b = 8 * pos - cnt
+        if final:
+            return end(EXIT_FINAL)
+        c = cands.get(b)
+        if c is not None and c == b // chunk_bits:
+            rec["next"] = c
+            return end(EXIT_LINK)
 
 
 def _unfilter(raw, H, rowbytes, bpp):
@@ -487,6 +737,74 @@ class PngImage(object):
             return 8, None
         return status, out
 
+    def parallel_plan(self, chunk_bytes):
+        """What ``io_png_decode_par`` does with this stream at ``chunk_bytes``, by the rule of csrc/png_inflate_par.h in
+        Python: the contract of the info word and the records.  dict(
+        chunks; starts: the candidate bit per chunk, -1 for none; records: per chunk with a candidate dict(exit, exit_bit,
+        n, reach, status, next), None otherwise; chain: the chunks the walk from chunk 0 visits; offsets: the output
+        offset of each of them; clean; info: the info word; parallel: clean with a chain of two or more;
+        symbols: per chain chunk the uint16 symbols (clean images only); resolved: the bytes they resolve to (parallel
+        images only, else None); stats: dict(markers: symbols that are markers after the store pass, markers_copied: markers
+        that a match copied from inside its chunk, max_reach, reach_chunks: chain chunks in front of it that the longest
+        reach spans, stored / fixed / dynamic: blocks decoded by the chain chunks)).  Slow: small files."""
+        chunk_bytes = _check_chunk_bytes(chunk_bytes, "parallel_plan")
+        data, expected = self._deflate, self.inflated_bytes
+        nb = len(data)
+        nchunks = (nb + chunk_bytes - 1) // chunk_bytes
+        if nchunks > PAR_MAX_CHUNKS:
+            raise ValueError("PNG image %s: %d chunks of %d bytes (at most %d)" % (self.name, nchunks, chunk_bytes, PAR_MAX_CHUNKS))
+        if getattr(self, "_headers_of", None) is not data:
+            self._headers, self._headers_of = np.array(dynamic_header_bits(data), np.int64), data
+        chunk_bits = 8 * chunk_bytes
+        starts = [-1] * nchunks
+        for c in range(nchunks):
+            if c == 0:
+                starts[c] = 0
+                continue
+            k = int(np.searchsorted(self._headers, c * chunk_bits))
+            if k < self._headers.size and self._headers[k] < min((c + 1) * chunk_bits, 8 * nb):
+                starts[c] = int(self._headers[k])
+        cands = {s: c for c, s in enumerate(starts) if s >= 0}
+        walks = [_chunk_walk(data, s, expected, cands, chunk_bits) if s >= 0 else None for s in starts]
+        chain, offsets, clean, off, c = [], [], False, 0, 0
+        while c < nchunks:
+            r = walks[c]
+            chain.append(c)
+            offsets.append(off)
+            if r["exit"] not in (EXIT_FINAL, EXIT_LINK) or r["reach"] > off or off + r["n"] > expected:
+                break
+            off += r["n"]
+            if r["exit"] == EXIT_FINAL:
+                clean = off == expected
+                break
+            if r["next"] <= c:
+                break
+            c = r["next"]
+        info = min(len(chain), 65535) | (0 if clean else INFO_NOT_CLEAN) | (INFO_CHAIN_OF_ONE if clean and len(chain) < 2 else 0)
+        stats = dict(markers=0, markers_copied=0, max_reach=0, reach_chunks=0, stored=0, fixed=0, dynamic=0)
+        resolved = None
+        if clean:
+            for idx, (c, o) in enumerate(zip(chain, offsets)):
+                r = walks[c]
+                stats["markers"] += sum(1 for v in r["syms"] if v >= 0x8000)
+                stats["markers_copied"] += r["copied"]
+                for k, name in enumerate(("stored", "fixed", "dynamic")):
+                    stats[name] += r["blocks"][k]
+                if r["reach"] > stats["max_reach"]:
+                    stats["max_reach"] = r["reach"]
+                    stats["reach_chunks"] = sum(1 for k in range(idx) if offsets[k + 1] > o - r["reach"])
+            if len(chain) >= 2:
+                out = bytearray(expected)
+                for c, o in zip(chain, offsets):
+                    for j, v in enumerate(walks[c]["syms"]):
+                        out[o + j] = out[o - 1 - (v & 0x7FFF)] if v >= 0x8000 else v
+                resolved = bytes(out)
+        keys = ("exit", "exit_bit", "n", "reach", "status", "next")
+        return dict(chunks=nchunks, starts=starts, records=[None if w is None else {k: w[k] for k in keys} for w in walks],
+                    chain=chain, offsets=offsets, clean=clean, info=info, parallel=clean and len(chain) >= 2,
+                    symbols=[np.array(walks[c]["syms"], np.uint16) for c in chain] if clean else None, resolved=resolved,
+                    stats=stats)
+
     def _inflate(self):
         d = zlib.decompressobj(-15)
         try:
@@ -536,19 +854,73 @@ def descriptors(images, out_offs):
     return pool, desc
 
 
-def workspace_bytes(desc):
-    b = int(_lib.lib().io_png_workspace_bytes(C.cast(desc, C.c_void_p), len(desc)))
+DEFAULT_CHUNK_BYTES = 1024
+_INFLATE = {"mode": "sequential", "chunk_bytes": DEFAULT_CHUNK_BYTES}
+
+
+def _check_chunk_bytes(chunk_bytes, who):
+    if isinstance(chunk_bytes, bool) or not isinstance(chunk_bytes, (int, np.integer)) or \
+            not PAR_MIN_CHUNK <= chunk_bytes <= PAR_MAX_CHUNK or chunk_bytes % PAR_MIN_CHUNK:
+        raise ValueError("png.%s: chunk_bytes %r (a multiple of %d in %d..%d)" % (who, chunk_bytes, PAR_MIN_CHUNK, PAR_MIN_CHUNK,
+                                                                                  PAR_MAX_CHUNK))
+    return int(chunk_bytes)
+
+
+def set_inflate(mode, chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """The inflate stage ``decode``, ``workspace_bytes`` / ``launch`` and with them ``PairRenderer`` and ``dense_eval`` use:
+    "sequential" -- one wave per image (``io_png_decode``) -- or "parallel" -- one stream on many waves from found block
+    starts (``io_png_decode_par``, csrc/png_inflate_par.h), chunks of ``chunk_bytes``.  Bytes and status words do not
+    depend on it.  Module-wide; the default is "sequential", the environment variable IO_PNG_INFLATE=parallel selects the
+    other at import."""
+    if mode not in ("sequential", "parallel"):
+        raise ValueError("png.set_inflate: mode %r ('sequential' or 'parallel')" % (mode,))
+    _INFLATE.update(mode=mode, chunk_bytes=_check_chunk_bytes(chunk_bytes, "set_inflate"))
+
+
+def get_inflate(inflate=None):
+    """a copy of the setting; ``inflate``: "sequential" / "parallel" instead of the module-wide mode, or a dict to pass on"""
+    if isinstance(inflate, dict):
+        return dict(inflate)
+    s = dict(_INFLATE)
+    if inflate is not None:
+        if inflate not in ("sequential", "parallel"):
+            raise ValueError("png: inflate %r ('sequential' or 'parallel')" % (inflate,))
+        s["mode"] = inflate
+    return s
+
+
+if os.environ.get("IO_PNG_INFLATE", ""):
+    set_inflate(os.environ["IO_PNG_INFLATE"])
+
+
+def workspace_bytes(desc, inflate=None):
+    s = get_inflate(inflate)
+    if s["mode"] == "parallel":
+        fn = "io_png_par_workspace_bytes"
+        b = int(_lib.lib().io_png_par_workspace_bytes(C.cast(desc, C.c_void_p), len(desc), s["chunk_bytes"]))
+    else:
+        fn = "io_png_workspace_bytes"
+        b = int(_lib.lib().io_png_workspace_bytes(C.cast(desc, C.c_void_p), len(desc)))
     if b == 0:
-        raise RuntimeError("instaorder_hip io_png_workspace_bytes refused the descriptors: %s" % _lib.last_error())
+        raise RuntimeError("instaorder_hip %s refused the descriptors: %s" % (fn, _lib.last_error()))
     return b
 
 
-def launch(pool, pool_bytes, desc_dev, desc, out, out_bytes, ws, ws_bytes, status, stream):
-    """one ``io_png_decode`` call.  Device addresses as ints; ``desc``: the host PngDesc array."""
-    rc = _lib.lib().io_png_decode(C.c_void_p(pool), C.c_size_t(pool_bytes), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p),
-                                  len(desc), C.c_void_p(out), C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes),
-                                  C.c_void_p(status), C.c_void_p(stream))
-    _lib.check(rc, "io_png_decode")
+def launch(pool, pool_bytes, desc_dev, desc, out, out_bytes, ws, ws_bytes, status, stream, inflate=None, info=None):
+    """one ``io_png_decode`` / ``io_png_decode_par`` call, as the setting (or ``inflate``, a mode or a ``get_inflate``
+    dict) says.  Device addresses as ints; ``desc``: the host PngDesc array; ``info``: the address of int32 info words
+    per image (parallel only) or None."""
+    s = get_inflate(inflate)
+    head = (C.c_void_p(pool), C.c_size_t(pool_bytes), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p), len(desc),
+            C.c_void_p(out), C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status))
+    if s["mode"] == "parallel":
+        rc = _lib.lib().io_png_decode_par(*(head + (s["chunk_bytes"], C.c_void_p(info), C.c_void_p(stream))))
+        _lib.check(rc, "io_png_decode_par")
+    else:
+        if info is not None:
+            raise ValueError("png.launch: info words exist with the parallel inflate stage only")
+        rc = _lib.lib().io_png_decode(*(head + (C.c_void_p(stream),)))
+        _lib.check(rc, "io_png_decode")
 
 
 def raise_for_status(status, images):
@@ -559,18 +931,25 @@ def raise_for_status(status, images):
                                                               for nm, s in bad))
 
 
-def decode(images, device, out=None, check=True):
+def decode(images, device, out=None, check=True, inflate=None, info=False):
     """list of supported ``PngImage`` -> list of device tensors, uint8 [H, W, 3] or uint16 [H, W] (raw16), through one
     ``io_png_decode`` call on the current stream: views of ``out``, a contiguous uint8 device tensor of at least the
     summed sizes (each rounded up to 16 bytes), when given.  Waits for the status words and raises RuntimeError naming
     the images that did not decode; with ``check=False`` it does not wait and returns (tensors, status tensor, images)
     for ``raise_for_status`` later.  A uint16 result may be viewed as int16 storage (``t.view(torch.int16)``), which is
-    how ``ext_ops.depth_errors_median`` takes its ground truth."""
+    how ``ext_ops.depth_errors_median`` takes its ground truth.  ``inflate``: "sequential" or "parallel" instead of the
+    ``set_inflate`` mode.  With ``info`` (parallel only) the int32 info words of ``io_png_decode_par`` follow the result as
+    a NumPy array (a device tensor with ``check=False``)."""
     import torch
+    setting = get_inflate(inflate)
+    if info and setting["mode"] != "parallel":
+        raise ValueError("png.decode: info words exist with the parallel inflate stage only")
     _lib.require_gpu()
     device = torch.device(device)
     images = list(images)
     if not images:
+        if info:
+            return ([], np.zeros(0, np.int32)) if check else ([], None, [], None)
         return [] if check else ([], None, [])
     for im in images:
         if not is_png(im):
@@ -592,11 +971,13 @@ def decode(images, device, out=None, check=True):
     host[:dbytes] = np.frombuffer(desc, dtype=np.uint8)
     host[dbytes:dbytes + pool.size] = pool
     dev = torch.from_numpy(host).to(out.device)
-    ws = torch.empty(workspace_bytes(desc), dtype=torch.uint8, device=out.device)
+    ws = torch.empty(workspace_bytes(desc, setting), dtype=torch.uint8, device=out.device)
     status = torch.empty(len(images), dtype=torch.int32, device=out.device)
+    words = torch.empty(len(images), dtype=torch.int32, device=out.device) if info else None
     base = dev.data_ptr()
     launch(base + dbytes, pool.size, base, desc, out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel(),
-           status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream)
+           status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream, setting,
+           words.data_ptr() if info else None)
     ws.record_stream(torch.cuda.current_stream(out.device))
     dev.record_stream(torch.cuda.current_stream(out.device))
     res = []
@@ -604,9 +985,9 @@ def decode(images, device, out=None, check=True):
         t = out[o:o + s]
         res.append(t.view(torch.uint16).view(im.H, im.W) if im.raw16 else t.view(im.H, im.W, 3))
     if not check:
-        return res, status, images
+        return (res, status, images, words) if info else (res, status, images)
     raise_for_status(status.cpu().numpy(), images)
-    return res
+    return (res, words.cpu().numpy()) if info else res
 
 
 def _pil_rgb(path):

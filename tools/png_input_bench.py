@@ -19,6 +19,15 @@ the rows of (b) must be equal bit for bit; otherwise the exit status is 1.  No t
 the device is reported as it is.
 
     python tools/png_input_bench.py [--B 64] [--S 256] [--batches 10] [--warmup 3] [--repeats 2] [--images 16] [--out profiles/png_input_bench.json]
+
+With ``--parallel`` the tool compares the two inflate stages instead (``png.set_inflate``): on the same files, for every
+``--chunk-bytes`` size, the sequential and the parallel setting alternate, --repeats times each, over the legs one frame
+alone, --images frames in one call (and the same for the depth maps), the training pipeline with ``png.PngImage`` and the
+dense evaluation's input side with ``png="device"``.  Per size it records chain chunks and fallbacks per file (the info
+words), the time of every stage class (search, count with the chain, store, resolve, the predicated sequential kernel
+with Adler-32, unfilter, pack) and Pillow's decode time from the same run.  Outputs must be equal bit for bit.
+
+    python tools/png_input_bench.py --parallel [--chunk-bytes 1024 4096 16384] [--out profiles/png_parallel_bench.json]
 """
 import argparse
 import io
@@ -132,6 +141,118 @@ def stages(ims, label):
                 inflate_ms=round(ms["png_inflate"], 3), unfilter_ms=round(ms["png_unfilter"], 3), pack_ms=round(ms["png_pack"], 4))
 
 
+PAR_CLASSES = ("png_par_search", "png_par_count", "png_par_store", "png_par_resolve", "png_inflate", "png_unfilter", "png_pack")
+
+
+def stages_setting(ims, mode, chunk_bytes):
+    """one decode call over ``ims`` under the setting after a warm one: (call ms, {class: ms}, outputs as bytes, info)"""
+    L = _lib.lib()
+    keep = png.get_inflate()
+    try:
+        png.set_inflate(mode, chunk_bytes)
+        png.decode(ims, "cuda")
+        torch.cuda.synchronize()
+        L.io_prof_begin_ex(0)
+        t = time.perf_counter()
+        got = png.decode(ims, "cuda", info=mode == "parallel")
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t
+        ent = (_lib.ProfEntry * 32)()
+        n = L.io_prof_end(ent, 32)
+    finally:
+        png.set_inflate(keep["mode"], keep["chunk_bytes"])
+    ms = {e.name.decode(): round(e.total_ms, 4) for e in ent[:n]}
+    tensors, info = got if mode == "parallel" else (got, None)
+    return 1e3 * wall, {k: ms.get(k, 0.0) for k in PAR_CLASSES}, [t.cpu().numpy().tobytes() for t in tensors], info
+
+
+def parallel_main(a):
+    """sequential against parallel inflate stage, leg by leg and size by size; the JSON result"""
+    import PIL
+    from PIL import Image
+    rd = synthetic.SyntheticReader(500, n_images=a.images, n_inst=8, max_side=640, min_side=480, empty_every=0)
+    rs = np.random.RandomState(77)
+    frames = [png_bytes(frame(9000 + i)) for i in range(a.images)]
+    depths = [png_bytes(synthetic.sparse_gt_u16(rs, H, W)) for i in range(a.images)]
+    files = {rd.get_image_instances(i)[4]: frames[i] for i in range(a.images)}
+    fr = [png.PngImage(b, name="frame %d" % i) for i, b in enumerate(frames)]
+    dp = [png.PngImage(b, name="depth %d" % i) for i, b in enumerate(depths)]
+    pil = {}
+    for label, blobs, rgb in (("frame", frames, True), ("depth", depths, False)):
+        t = time.perf_counter()
+        for b in blobs:
+            im = Image.open(io.BytesIO(b))
+            np.array(im.convert("RGB") if rgb else im)
+        pil[label + "_ms_per_image"] = round(1e3 * (time.perf_counter() - t) / len(blobs), 3)
+    ok = True
+    sizes = {}
+    with tempfile.TemporaryDirectory() as root:
+        lst = write_kitti(root, frames, depths)
+        for cb in a.chunk_bytes:
+            # the stages alone
+            alone = []
+            for label, ims in (("1 frame", fr[:1]), ("%d frames" % a.images, fr), ("1 depth map", dp[:1]),
+                               ("%d depth maps" % a.images, dp)):
+                legs = {"sequential": [], "parallel": []}
+                ref, info = None, None
+                for rep in range(a.repeats):
+                    for mode in ("sequential", "parallel"):
+                        wall, ms, out, words = stages_setting(ims, mode, cb)
+                        legs[mode].append(dict(call_ms=round(wall, 3), classes_ms=ms))
+                        ref = out if ref is None else ref
+                        ok = ok and out == ref
+                        info = words if words is not None else info
+                inflate = {m: spread([sum(v for k, v in leg["classes_ms"].items() if k not in ("png_unfilter", "png_pack"))
+                                      for leg in legs[m]]) for m in legs}
+                alone.append(dict(files=label, images=len(ims), legs=legs, inflate_ms=inflate,
+                                  call_ms={m: spread([leg["call_ms"] for leg in legs[m]]) for m in legs},
+                                  chain_chunks=[int(w) & 0xFFFF for w in info], fallbacks=int(sum(int(w) >> 16 != 0 for w in info))))
+            # the training pipeline and the dense evaluation's input side
+            runs = {"sequential": [], "parallel": []}
+            secs = {"sequential": [], "parallel": []}
+            firsts, rows = [], []
+            for rep in range(a.repeats):
+                for mode in ("sequential", "parallel"):
+                    png.set_inflate(mode, cb)
+                    try:
+                        reader = FrameReader(rd, files, "png")
+                        res, first = base.leg("PngImage, %s inflate at %d, repeat %d" % (mode, cb, rep), reader, a)
+                        runs[mode].append(res)
+                        firsts.append(first)
+                        for warm in (True, False):
+                            kr = dense_eval.KITTIEigenReader(lst, root, png="device")
+                            torch.cuda.synchronize()
+                            t = time.perf_counter()
+                            r = dense_eval.eval_dense_depth(ConstantNet(), kr, "midas_pretrained", batch=4, return_rows=True)
+                            torch.cuda.synchronize()
+                            if not warm:
+                                secs[mode].append(1e3 * (time.perf_counter() - t) / a.images)
+                        rows.append(r["rows"].tobytes())
+                    finally:
+                        png.set_inflate("sequential")
+            ok = ok and all(np.array_equal(x, y) for f in firsts[1:] for x, y in zip(firsts[0], f)) and len(set(rows)) == 1
+            sizes[str(cb)] = dict(stages_alone=alone,
+                                  training_batch_ms_median={m: spread([r["batch_ms_median"] for r in runs[m]]) for m in runs},
+                                  dense_eval_ms_per_image={m: spread(secs[m]) for m in secs})
+        kr = dense_eval.KITTIEigenReader(lst, root, png="host")
+        host = []
+        for warm in (True, False, False):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            dense_eval.eval_dense_depth(ConstantNet(), kr, "midas_pretrained", batch=4, return_rows=True)
+            torch.cuda.synchronize()
+            if not warm:
+                host.append(1e3 * (time.perf_counter() - t) / a.images)
+    return dict(tool="tools/png_input_bench.py --parallel", device=torch.cuda.get_device_name(0), csrc_digest=_lib.csrc_digest(),
+                B=a.B, S=a.S, batches=a.batches, warmup=a.warmup, repeats=a.repeats, images=a.images,
+                files="%d x %d RGB frames (smooth picture, noise 0..3) and 16-bit depth maps (about 5 %% valid), written by "
+                      "Pillow %s with its default settings" % (W, H, PIL.__version__),
+                frame_file_bytes_mean=round(float(np.mean([len(b) for b in frames])), 1),
+                depth_file_bytes_mean=round(float(np.mean([len(b) for b in depths])), 1),
+                pillow_decode=pil, dense_eval_host_ms_per_image=spread(host), chunk_bytes=sizes, outputs_equal=bool(ok),
+                not_measured="real KITTI files; the pipelines beside a network step; a multi-threaded host decoder"), ok
+
+
 def spread(v):
     return dict(median=round(float(np.median(v)), 3), min=round(min(v), 3), max=round(max(v), 3), samples=len(v))
 
@@ -146,12 +267,29 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--images", type=int, default=16)
     ap.add_argument("--out", default="")
+    ap.add_argument("--parallel", action="store_true", help="compare the sequential and the parallel inflate stage")
+    ap.add_argument("--chunk-bytes", type=int, nargs="+", default=[1024, 4096, 16384])
     a = ap.parse_args(argv)
     assert a.batches >= 1 and a.warmup >= 1 and a.probe >= 1 and a.repeats >= 1 and a.images >= 1
     import PIL
     from PIL import Image
     _lib.require_gpu()
     torch.cuda.set_device(0)
+    if a.parallel:
+        res, ok = parallel_main(a)
+        print(json.dumps({k: v for k, v in res.items() if k != "chunk_bytes"}), flush=True)
+        for cb, r in res["chunk_bytes"].items():
+            print(json.dumps({"chunk_bytes": int(cb), "training_batch_ms_median": r["training_batch_ms_median"],
+                              "dense_eval_ms_per_image": r["dense_eval_ms_per_image"],
+                              "stages_alone": [{k: s[k] for k in ("files", "inflate_ms", "call_ms", "fallbacks")}
+                                               for s in r["stages_alone"]]}), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+                f.write("\n")
+        if not ok:
+            print("FAILED: the legs differ")
+        return 0 if ok else 1
     rd = synthetic.SyntheticReader(500, n_images=a.images, n_inst=8, max_side=640, min_side=480, empty_every=0)
     rs = np.random.RandomState(77)
     frames = [png_bytes(frame(9000 + i)) for i in range(a.images)]
