@@ -144,6 +144,9 @@ def _cfg(algo):
 
 @pytest.mark.parametrize("algo,S,B", [("InstaOrderNet_o", 64, 4), ("InstaOrderNet_od", 128, 4)])
 def test_network_bf16_vs_fp32_oracle(algo, S, B):
+    """The end-to-end bf16 check: logits, loss and the global gradient against the fp32 oracle on a damped network.  The
+    per-block bars (every stored block output and every parameter tensor against an fp64 oracle, per route) live in
+    test_gpu_step_blocks.py; this test remains the end-to-end one."""
     import instaorder_amd as ia
     m = getattr(ia, algo)(_cfg(algo), dist_model=False)
     assert m.net.dtype == "bf16"
