@@ -791,6 +791,60 @@ int io_jpeg_decode_par_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_j
 int io_jpeg_set_images_per_wave(int images);
 int io_jpeg_get_images_per_wave(void);
 int io_jpeg_lds_table_sets(void);   /* IO_JPEG_LDS_TABLE_SETS of the built library */
+/* Progressive (SOF2) files (csrc/jpeg_prog.h, DESIGN.md "Progressive JPEG"; opt-in, the baseline entry points are
+ * unchanged).  Stages (2) and (3) are those of io_jpeg_decode_u8; stage (1) fills the same coefficient range over the many
+ * scans of a file (T.81 G.1.2: DC first / refinement, AC first with EOBRUN, AC refinement with correction bits).  Per image
+ * an io_jpeg_desc gives the geometry, the quantisation indices, table_set (its quant tables only; dc, ac, data_off,
+ * data_bytes and restart_interval are not read) and out_off, and an io_jpeg_prog_image its scans: n_scans consecutive
+ * entries of the scan table from first_scan, in file order, the images' ranges following each other without gaps.  A scan
+ * names its entropy-coded bytes in the pool, its components (frame order), Ss, Se, Ah, Al, its restart interval, per
+ * component an index into a pool of raw Huffman tables (the DC table in a DC first scan, the AC table in an AC scan; not
+ * read in a DC refinement) and its LEVEL.  One 256-thread block per image loops over the image's levels with a block
+ * barrier between them; the scans of a level run side by side, each on one lane of a wave of its own (more than four in
+ * several passes).  concurrent = 0 runs all scans of an image in file order on one lane instead; output bytes and status
+ * words do not depend on it.  Every scan of an image runs and stops at its own fault; status_dev[i] is the first non-zero
+ * scan status in file order (the codes of io_jpeg_decode_u8; a refinement symbol whose size is not 1 counts as 1), the
+ * image is still written and no other image is affected.
+ *   Validated on the host copies before anything is enqueued (IO_ERR_SHAPE): the descriptors as for io_jpeg_decode_u8; the
+ * scan ranges; per scan 1 or all components in increasing frame order, a DC scan Ss = Se = 0, an AC scan one component and
+ * 1 <= Ss <= Se <= 63, Al <= 13, Ah = 0 for the first scan of a coefficient and Ah = Al + 1 = the previous Al of every
+ * coefficient of its band for a refinement, no AC scan of a component in front of its first DC scan, every coefficient of
+ * every component sent and refined down to Al = 0; table indices inside the pool and every referenced table a prefix code
+ * of at most 256 symbols; data inside the byte pool, output inside out_bytes; and the LEVEL RULE: a scan's level is below
+ * the image's n_levels and strictly above the level of every earlier scan of its image that shares a (component,
+ * coefficient) pair with it -- scans of one level therefore touch disjoint coefficients, which is what keeps the kernel free
+ * of data races, so the library checks it and does not trust the caller.  IO_ERR_WORKSPACE for a workspace below
+ * io_jpeg_prog_workspace_bytes() (0: refused): that of io_jpeg_decode_u8 with 904 bytes per raw table instead of the
+ * derived tables per set, plus a status word per scan.  Whatever the pool and table BYTES are, a scan decodes at most
+ * Se - Ss + 2 symbols per block, visits a coefficient at most once, reads pool bytes of its own range only and stores
+ * inside its image's coefficient range. */
+typedef struct io_jpeg_huff_raw {
+    uint8_t counts[16];        /* codes of length 1..16 (DHT) */
+    uint8_t symbols[256];      /* symbols in code order */
+} io_jpeg_huff_raw;
+typedef struct io_jpeg_prog_scan {
+    int64_t data_off;          /* first byte of the scan's entropy-coded segment in the pool */
+    int32_t data_bytes;
+    int32_t image;             /* the image the scan belongs to */
+    int32_t restart_interval;  /* MCUs of this scan between RSTn markers, 0: none */
+    int32_t level;
+    int32_t table[3];          /* per scan component: index into the raw Huffman tables */
+    uint8_t n_comp;            /* components of the scan */
+    uint8_t comp[3];           /* their indices in the frame, increasing */
+    uint8_t ss, se, ah, al;
+    int32_t reserved[5];
+} io_jpeg_prog_scan;
+typedef struct io_jpeg_prog_image {
+    int32_t first_scan, n_scans, n_levels, reserved;
+} io_jpeg_prog_image;
+int io_jpeg_decode_prog_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev,
+                           const io_jpeg_tables* tables_host, size_t tables_bytes, const io_jpeg_huff_raw* huff_dev,
+                           const io_jpeg_huff_raw* huff_host, int n_huff, const io_jpeg_desc* desc_dev,
+                           const io_jpeg_desc* desc_host, const io_jpeg_prog_image* image_dev,
+                           const io_jpeg_prog_image* image_host, int n, const io_jpeg_prog_scan* scan_dev,
+                           const io_jpeg_prog_scan* scan_host, int n_scans, uint8_t* out, size_t out_bytes, void* workspace,
+                           size_t workspace_bytes, int32_t* status_dev, int concurrent, hipStream_t stream);
+size_t io_jpeg_prog_workspace_bytes(const io_jpeg_desc* desc_host, int n, int n_huff, int n_scans);
 
 /* ---- PNG images and 16-bit depth maps decoded on the device (csrc/png.hip, csrc/png_inflate.h, DESIGN.md "PNG images"),
  * in front of io_pair_planes_u8_hw or of io_depth_errors_median.  The caller parses the chunks; what travels is the zlib

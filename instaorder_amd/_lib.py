@@ -66,6 +66,23 @@ class JpegDesc(C.Structure):
                 ("ac", C.c_uint8 * 4), ("reserved", C.c_int32)]
 
 
+class JpegHuffRaw(C.Structure):
+    """io_jpeg_huff_raw of include/instaorder_hip.h"""
+    _fields_ = [("counts", C.c_uint8 * 16), ("symbols", C.c_uint8 * 256)]
+
+
+class JpegProgScan(C.Structure):
+    """io_jpeg_prog_scan of include/instaorder_hip.h"""
+    _fields_ = [("data_off", C.c_int64), ("data_bytes", C.c_int32), ("image", C.c_int32), ("restart_interval", C.c_int32),
+                ("level", C.c_int32), ("table", C.c_int32 * 3), ("n_comp", C.c_uint8), ("comp", C.c_uint8 * 3),
+                ("ss", C.c_uint8), ("se", C.c_uint8), ("ah", C.c_uint8), ("al", C.c_uint8), ("reserved", C.c_int32 * 5)]
+
+
+class JpegProgImage(C.Structure):
+    """io_jpeg_prog_image of include/instaorder_hip.h"""
+    _fields_ = [("first_scan", C.c_int32), ("n_scans", C.c_int32), ("n_levels", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PngDesc(C.Structure):
     """io_png_desc of include/instaorder_hip.h"""
     _fields_ = [("data_off", C.c_int64), ("out_off", C.c_int64), ("data_bytes", C.c_int32), ("H", C.c_int32),
@@ -144,6 +161,10 @@ SIGNATURES = {
     # the arguments of io_jpeg_decode_u8 up to status_dev, then subseq_bytes, max_rounds, info_dev, stream
     "io_jpeg_decode_par_u8": (_I, [_P, _Z, _P, _P, _Z, _P, _P, _I, _P, _Z, _P, _Z, _P, _I, _I, _P, _P]),
     "io_jpeg_par_workspace_bytes": (_Z, [_P, _I, _I]),
+    # pool_dev, pool_bytes, tables_dev, tables_host, tables_bytes, huff_dev, huff_host, n_huff, desc_dev, desc_host, image_dev,
+    # image_host, n, scan_dev, scan_host, n_scans, out, out_bytes, workspace, workspace_bytes, status_dev, concurrent, stream
+    "io_jpeg_decode_prog_u8": (_I, [_P, _Z, _P, _P, _Z, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _Z, _P, _Z, _P, _I, _P]),
+    "io_jpeg_prog_workspace_bytes": (_Z, [_P, _I, _I, _I]),
     "io_jpeg_set_images_per_wave": (_I, [_I]),
     "io_jpeg_get_images_per_wave": (_I, []),
     "io_jpeg_lds_table_sets": (_I, []),

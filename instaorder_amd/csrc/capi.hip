@@ -214,7 +214,7 @@ const char* kProfNames[IO_PROF_NCLASS] = {"conv_nt_kernel<128,false>", "conv_nt_
     "conv_nt_kernel<64,true>", "conv_wgrad_kernel", "conv_wgrad_kernel<64,64,true>", "bn_stats_finalize",
     "bn_apply", "bn_bwd", "pool_head", "filter_transpose", "pack_planes", "order_loss", "sgd_momentum",
     "conv_nt_kernel<wino>", "conv_wgrad_kernel<wino>", "adam", "grad_norm", "rle_decode", "poly_fill",
-    "jpeg_entropy", "jpeg_idct", "jpeg_colour", "png_inflate", "png_unfilter", "png_pack",
+    "jpeg_entropy", "jpeg_idct", "jpeg_colour", "jpeg_prog_entropy", "png_inflate", "png_unfilter", "png_pack",
     "png_par_search", "png_par_count", "png_par_store", "png_par_resolve"};
 hipEvent_t prof_event() {
     if (!g_prof_pool.empty()) { hipEvent_t e = g_prof_pool.back(); g_prof_pool.pop_back(); return e; }

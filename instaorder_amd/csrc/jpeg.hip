@@ -18,15 +18,20 @@
 //      jpeg_fallback_kernel  self-synchronising scheme of jpeg_sync.h -- threads stride over the subsequences of the scan, the
 //                            rounds loop inside the kernel -- and stores the coefficients of a clean image; every other
 //                            image is decoded by the one-lane loop of stage 1, launched behind it with a per-image predicate.
+//   1g. jpeg_prog_entropy_kernel (io_jpeg_decode_prog_u8 only) stage 1 of PROGRESSIVE files (jpeg_prog.h): one 256-thread block per
+//                            image fills the coefficient range over the file's scans, level by level with a block barrier
+//                            between levels, the scans of a level on one lane each of different waves.
 // All arithmetic is 32-bit two's complement, which holds every intermediate of a stream an encoder made from 8-bit samples.
 //
 // Safety does not depend on the pool or table bytes: see jpeg_entropy.h for stage 1; stages 2 and 3 read and write only
 // addresses that follow from the descriptors the host validated, and every sample is clamped to a byte before it is stored.
 #include "io_common.h"
 #include "jpeg_entropy.h"
+#include "jpeg_prog.h"
 #include "jpeg_sync.h"
 
 #include <atomic>
+#include <vector>
 
 namespace {
 
@@ -671,4 +676,233 @@ extern "C" int io_jpeg_decode_par_u8(const uint8_t* pool_dev, size_t pool_bytes,
     }
     jpeg_launch_pixels(plan, tables_dev, desc_dev, off, coef, planes, out, n, st);
     return io_check_launch("jpeg_decode_par");
+}
+
+// ---- progressive files (jpeg_prog.h) ---------------------------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(io_jpeg_prog_scan) == 64 && sizeof(io_jpeg_prog_image) == 16 && sizeof(io_jpeg_huff_raw) == 272,
+              "ABI layout of the progressive JPEG tables");
+
+__global__ __launch_bounds__(64) void jpeg_prog_tables_kernel(const io_jpeg_huff_raw* __restrict__ raw, JpegHuff* __restrict__ huff,
+                                                              int n_huff) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t < n_huff) (void)jpeg_build_huff(raw[t].counts, raw[t].symbols, huff + t);
+}
+
+__device__ __forceinline__ int prog_run_scan(const io_jpeg_prog_scan& sc, const io_jpeg_desc& d, const uint8_t* __restrict__ pool,
+                                             const JpegHuff* __restrict__ huff, int16_t* __restrict__ coef) {
+    JpegProgScan s;
+    s.data = pool + sc.data_off;
+    s.nbytes = sc.data_bytes;
+    s.n_scan_comp = sc.n_comp;
+    s.comp = sc.comp[0];
+    s.ss = sc.ss;
+    s.se = sc.se;
+    s.ah = sc.ah;
+    s.al = sc.al;
+    s.restart_interval = sc.restart_interval;
+    const bool dc_refine = sc.ss == 0 && sc.ah != 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) s.tab[j] = huff + (dc_refine || j >= sc.n_comp ? 0 : sc.table[j]);    // the host checked the indices
+    s.W = d.W;
+    s.H = d.H;
+    s.n_comp = d.n_comp;
+    s.hs = d.hs;
+    s.vs = d.vs;
+    return jpeg_prog_decode_scan(s, coef);
+}
+
+// One block per image.  concurrent: the block walks the image's levels, a barrier behind each; inside a level the ready scans
+// are dealt to the four waves in turn and run on lane 0 of their wave (a level of more than four scans takes several turns of
+// a wave).  Scans of one level touch disjoint coefficients (the host checked the levels), and a coefficient an earlier level
+// stored is read behind that level's barrier.  The number of barriers is the image's n_levels for every thread and no thread
+// returns in front of the last one.  Not concurrent: thread 0 runs the scans in file order, no barrier at all.
+__global__ __launch_bounds__(kThreads) void jpeg_prog_entropy_kernel(const uint8_t* __restrict__ pool, const JpegHuff* __restrict__ huff,
+                                                                     const io_jpeg_desc* __restrict__ desc,
+                                                                     const io_jpeg_prog_image* __restrict__ images,
+                                                                     const io_jpeg_prog_scan* __restrict__ scans,
+                                                                     const unsigned long long* __restrict__ off,
+                                                                     int16_t* __restrict__ coef, int32_t* __restrict__ scan_status,
+                                                                     int32_t* __restrict__ status, int concurrent) {
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const io_jpeg_prog_image im = images[img];
+    const io_jpeg_desc d = desc[img];
+    int16_t* dst = coef + 64 * (long)off[img];
+    const io_jpeg_prog_scan* mine = scans + im.first_scan;
+    int32_t* mine_status = scan_status + im.first_scan;
+    if (!concurrent) {                                           // block-uniform
+        if (tid == 0) {
+            int first = 0;
+            for (int s = 0; s < im.n_scans; ++s) {
+                const int st = prog_run_scan(mine[s], d, pool, huff, dst);
+                if (first == 0) first = st;
+            }
+            status[img] = first;
+        }
+        return;
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int level = 0; level < im.n_levels; ++level) {          // block-uniform trip count
+        if (lane == 0) {
+            int seen = 0;
+            for (int s = 0; s < im.n_scans; ++s) {
+                if (mine[s].level != level) continue;
+                if ((seen++ & (kThreads / 64 - 1)) == wave) mine_status[s] = prog_run_scan(mine[s], d, pool, huff, dst);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        int first = 0;
+        for (int s = 0; s < im.n_scans && first == 0; ++s) first = mine_status[s];
+        status[img] = first;
+    }
+}
+
+struct JpegProgPlan {
+    size_t huff_bytes, scan_status_bytes;
+};
+
+int jpeg_prog_plan(int n_huff, int n_scans, JpegProgPlan* pp) {
+    IO_REQUIRE(n_huff >= 1 && n_huff <= 65535, IO_ERR_SHAPE, "jpeg_decode_prog: n_huff=%d (1..65535 Huffman tables)", n_huff);
+    IO_REQUIRE(n_scans >= 1 && n_scans <= (1 << 24), IO_ERR_SHAPE, "jpeg_decode_prog: n_scans=%d (1..2^24)", n_scans);
+    pp->huff_bytes = ((size_t)n_huff * sizeof(JpegHuff) + 15) / 16 * 16;
+    pp->scan_status_bytes = ((size_t)n_scans * sizeof(int32_t) + 15) / 16 * 16;
+    return IO_OK;
+}
+
+// the scan rules of DESIGN.md "Progressive JPEG" and the level rule, on the host tables
+int jpeg_prog_check_scans(const io_jpeg_desc* desc, const io_jpeg_prog_image* images, int n, const io_jpeg_prog_scan* scans, int n_scans,
+                          const io_jpeg_huff_raw* huff_host, int n_huff, size_t pool_bytes) {
+    std::vector<uint8_t> used((size_t)n_huff, 0);
+    long next = 0;
+    for (int i = 0; i < n; ++i) {
+        const io_jpeg_prog_image& im = images[i];
+        const io_jpeg_desc& d = desc[i];
+        IO_REQUIRE(im.first_scan == next && im.n_scans >= 1 && im.n_scans <= n_scans - next, IO_ERR_SHAPE,
+                   "jpeg_decode_prog: image %d has scans [%d, %d + %d): the ranges must follow each other inside the %d scans", i,
+                   im.first_scan, im.first_scan, im.n_scans, n_scans);
+        IO_REQUIRE(im.n_levels >= 1 && im.n_levels <= im.n_scans, IO_ERR_SHAPE, "jpeg_decode_prog: image %d has n_levels=%d for %d scans",
+                   i, im.n_levels, im.n_scans);
+        next += im.n_scans;
+        int al_of[3][64], level_of[3][64];                       // per coefficient: the Al it was sent down to, the level of its last scan
+        for (int c = 0; c < 3; ++c)
+            for (int k = 0; k < 64; ++k) al_of[c][k] = level_of[c][k] = -1;
+        for (int s = 0; s < im.n_scans; ++s) {
+            const int g = im.first_scan + s;
+            const io_jpeg_prog_scan& sc = scans[g];
+            IO_REQUIRE(sc.image == i, IO_ERR_SHAPE, "jpeg_decode_prog: scan %d names image %d inside the range of image %d", g, sc.image, i);
+            IO_REQUIRE(sc.n_comp >= 1 && sc.n_comp <= 3 && (sc.n_comp == 1 || sc.n_comp == d.n_comp), IO_ERR_SHAPE,
+                       "jpeg_decode_prog: scan %d has %d of the image's %d components (1 or all)", g, sc.n_comp, d.n_comp);
+            for (int j = 0; j < sc.n_comp; ++j)
+                IO_REQUIRE(sc.comp[j] < d.n_comp && (j == 0 || sc.comp[j] > sc.comp[j - 1]), IO_ERR_SHAPE,
+                           "jpeg_decode_prog: scan %d component list is not in increasing frame order below %d", g, d.n_comp);
+            IO_REQUIRE(sc.ss <= sc.se && sc.se <= 63 && (sc.ss == 0 ? sc.se == 0 : sc.n_comp == 1), IO_ERR_SHAPE,
+                       "jpeg_decode_prog: scan %d has Ss=%d Se=%d with %d components (a DC scan Ss = Se = 0, an AC scan one component and "
+                       "1 <= Ss <= Se <= 63)", g, sc.ss, sc.se, sc.n_comp);
+            IO_REQUIRE(sc.al <= 13 && (sc.ah == 0 || sc.ah == sc.al + 1), IO_ERR_SHAPE,
+                       "jpeg_decode_prog: scan %d has Ah=%d Al=%d (Al <= 13; Ah 0 or Al + 1)", g, sc.ah, sc.al);
+            IO_REQUIRE(sc.restart_interval >= 0, IO_ERR_SHAPE, "jpeg_decode_prog: scan %d has restart_interval=%d", g, sc.restart_interval);
+            IO_REQUIRE(sc.level >= 0 && sc.level < im.n_levels, IO_ERR_SHAPE, "jpeg_decode_prog: scan %d has level %d of %d", g, sc.level,
+                       im.n_levels);
+            IO_REQUIRE(sc.data_off >= 0 && sc.data_bytes >= 0 && (size_t)sc.data_off <= pool_bytes &&
+                           (size_t)sc.data_bytes <= pool_bytes - (size_t)sc.data_off,
+                       IO_ERR_SHAPE, "jpeg_decode_prog: scan %d data outside the byte pool", g);
+            for (int j = 0; j < sc.n_comp; ++j) {
+                const int c = sc.comp[j];
+                IO_REQUIRE(sc.ss == 0 || al_of[c][0] >= 0, IO_ERR_SHAPE,
+                           "jpeg_decode_prog: scan %d is an AC scan of component %d in front of its first DC scan", g, c);
+                for (int k = sc.ss; k <= sc.se; ++k) {
+                    IO_REQUIRE(sc.ah == 0 ? al_of[c][k] < 0 : al_of[c][k] == sc.ah, IO_ERR_SHAPE,
+                               "jpeg_decode_prog: scan %d (Ah=%d) meets coefficient %d of component %d at Al=%d (a first scan: not sent "
+                               "before; a refinement: Ah = the previous Al)", g, sc.ah, k, c, al_of[c][k]);
+                    IO_REQUIRE(sc.level > level_of[c][k], IO_ERR_SHAPE,
+                               "jpeg_decode_prog: scan %d has level %d, not above level %d of an earlier scan that shares coefficient %d "
+                               "of component %d", g, sc.level, level_of[c][k], k, c);
+                    al_of[c][k] = sc.al;
+                    level_of[c][k] = sc.level;
+                }
+                if (!(sc.ss == 0 && sc.ah != 0)) {
+                    IO_REQUIRE(sc.table[j] >= 0 && sc.table[j] < n_huff, IO_ERR_SHAPE,
+                               "jpeg_decode_prog: scan %d names Huffman table %d outside the pool of %d", g, sc.table[j], n_huff);
+                    used[(size_t)sc.table[j]] = 1;
+                }
+            }
+        }
+        for (int c = 0; c < d.n_comp; ++c)
+            for (int k = 0; k < 64; ++k)
+                IO_REQUIRE(al_of[c][k] == 0, IO_ERR_SHAPE,
+                           "jpeg_decode_prog: image %d is an incomplete progression: coefficient %d of component %d %s", i, k, c,
+                           al_of[c][k] < 0 ? "is never sent" : "is not refined down to Al = 0");
+    }
+    IO_REQUIRE(next == n_scans, IO_ERR_SHAPE, "jpeg_decode_prog: the images name %ld of the %d scans", next, n_scans);
+    for (int t = 0; t < n_huff; ++t) {
+        if (!used[(size_t)t]) continue;
+        JpegHuff h;
+        IO_REQUIRE(jpeg_build_huff(huff_host[t].counts, huff_host[t].symbols, &h), IO_ERR_SHAPE,
+                   "jpeg_decode_prog: Huffman table %d: the code lengths form no prefix code of at most 256 symbols", t);
+    }
+    return IO_OK;
+}
+
+}  // namespace
+
+extern "C" size_t io_jpeg_prog_workspace_bytes(const io_jpeg_desc* desc_host, int n, int n_huff, int n_scans) {
+    JpegPlan plan;
+    JpegProgPlan pp;
+    if (jpeg_check_desc(desc_host, n, &plan) != IO_OK || jpeg_prog_plan(n_huff, n_scans, &pp) != IO_OK) return 0;
+    return plan.off_bytes + pp.huff_bytes + plan.coef_bytes + plan.plane_bytes + pp.scan_status_bytes;
+}
+
+extern "C" int io_jpeg_decode_prog_u8(const uint8_t* pool_dev, size_t pool_bytes, const io_jpeg_tables* tables_dev,
+                                      const io_jpeg_tables* tables_host, size_t tables_bytes, const io_jpeg_huff_raw* huff_dev,
+                                      const io_jpeg_huff_raw* huff_host, int n_huff, const io_jpeg_desc* desc_dev,
+                                      const io_jpeg_desc* desc_host, const io_jpeg_prog_image* image_dev,
+                                      const io_jpeg_prog_image* image_host, int n, const io_jpeg_prog_scan* scan_dev,
+                                      const io_jpeg_prog_scan* scan_host, int n_scans, uint8_t* out, size_t out_bytes, void* workspace,
+                                      size_t workspace_bytes, int32_t* status_dev, int concurrent, hipStream_t st) {
+    IO_REQUIRE(pool_dev && tables_dev && tables_host && huff_dev && huff_host && desc_dev && desc_host && image_dev && image_host &&
+                   scan_dev && scan_host && out && workspace && status_dev,
+               IO_ERR_SHAPE, "jpeg_decode_prog: null pointer");
+    IO_REQUIRE(concurrent == 0 || concurrent == 1, IO_ERR_SHAPE, "jpeg_decode_prog: concurrent=%d (0 or 1)", concurrent);
+    JpegPlan plan;
+    JpegProgPlan pp;
+    int rc = jpeg_check_desc(desc_host, n, &plan);
+    if (rc != IO_OK) return rc;
+    rc = jpeg_prog_plan(n_huff, n_scans, &pp);
+    if (rc != IO_OK) return rc;
+    IO_REQUIRE((size_t)plan.n_sets * sizeof(io_jpeg_tables) <= tables_bytes, IO_ERR_SHAPE,
+               "jpeg_decode_prog: table set %d outside the %zu table bytes", plan.n_sets - 1, tables_bytes);
+    for (int i = 0; i < n; ++i) {
+        const io_jpeg_desc& d = desc_host[i];
+        const size_t nb = 3 * (size_t)d.H * (size_t)d.W;
+        IO_REQUIRE(d.out_off >= 0 && (size_t)d.out_off <= out_bytes && nb <= out_bytes - (size_t)d.out_off, IO_ERR_SHAPE,
+                   "jpeg_decode_prog: image %d output outside the output buffer", i);
+    }
+    rc = jpeg_prog_check_scans(desc_host, image_host, n, scan_host, n_scans, huff_host, n_huff, pool_bytes);
+    if (rc != IO_OK) return rc;
+    IO_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)tables_dev & 15) == 0 && ((uintptr_t)desc_dev & 7) == 0 &&
+                   ((uintptr_t)scan_dev & 7) == 0 && ((uintptr_t)image_dev & 3) == 0,
+               IO_ERR_SHAPE,
+               "jpeg_decode_prog: workspace and tables must be 16-byte aligned, descriptors and scans 8-byte, image records 4-byte aligned");
+    const size_t need = plan.off_bytes + pp.huff_bytes + plan.coef_bytes + plan.plane_bytes + pp.scan_status_bytes;
+    IO_REQUIRE(workspace_bytes >= need, IO_ERR_WORKSPACE, "jpeg_decode_prog: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    unsigned long long* off = reinterpret_cast<unsigned long long*>(ws);
+    JpegHuff* huff = reinterpret_cast<JpegHuff*>(ws + plan.off_bytes);
+    int16_t* coef = reinterpret_cast<int16_t*>(ws + plan.off_bytes + pp.huff_bytes);
+    uint8_t* planes = ws + plan.off_bytes + pp.huff_bytes + plan.coef_bytes;
+    int32_t* scan_status = reinterpret_cast<int32_t*>(planes + plan.plane_bytes);
+    const hipError_t e = hipMemsetAsync(coef, 0, plan.coef_bytes, st);
+    IO_REQUIRE(e == hipSuccess, IO_ERR_LAUNCH, "jpeg_decode_prog: clearing the coefficients: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(jpeg_offsets_kernel, dim3(1), dim3(kThreads), 0, st, desc_dev, n, off);
+    hipLaunchKernelGGL(jpeg_prog_tables_kernel, dim3(io_cdiv(n_huff, 64)), dim3(64), 0, st, huff_dev, huff, n_huff);
+    {
+        IoProfScope prof(IO_PROF_JPEG_PROG_ENTROPY, 0.0, (double)pool_bytes + (double)plan.coef_bytes, st);
+        hipLaunchKernelGGL(jpeg_prog_entropy_kernel, dim3(n), dim3(kThreads), 0, st, pool_dev, huff, desc_dev, image_dev, scan_dev, off, coef,
+                           scan_status, status_dev, concurrent);
+    }
+    jpeg_launch_pixels(plan, tables_dev, desc_dev, off, coef, planes, out, n, st);
+    return io_check_launch("jpeg_decode_prog");
 }

@@ -210,11 +210,11 @@ class PairRenderer(object):
         """render() for a batch in which at least one image carries ``rle.RLEMasks`` or ``poly.PolyMasks``, or is a
         ``jpeg.JpegImage`` or a ``png.PngImage``.  The arena lives on the device and only part of it is uploaded: one device buffer [array images
         and dense masks | run tables | decode descriptors | vertices | part and mask descriptors | entropy bytes | JPEG
-        tables and descriptors | PNG stream bytes and descriptors | pair descriptors | decoded masks and images | polygon
-        workspace | JPEG workspace and status | PNG workspace and status], of which everything before the decoded part comes through the pinned staging buffer in one copy.  One
+        tables and descriptors | PNG stream bytes and descriptors | tables, scans and bytes of progressive JPEG files | pair descriptors | decoded masks and images | polygon
+        workspace | JPEG workspace and status | PNG workspace and status | progressive JPEG workspace and status], of which everything before the decoded part comes through the pinned staging buffer in one copy.  One
         ``io_rle_decode_u8`` launch fills the slot of every referenced run-length mask, one ``io_poly_fill_u8`` call the
         slot of every referenced polygon instance and one ``io_jpeg_decode_u8`` call the slot of every referenced JPEG
-        image and one ``io_png_decode`` call the slot of every referenced PNG image, then ``io_pair_planes_u8_hw`` runs on the arena as it does for dense arrays.  (A batch without polygons,
+        image (one ``io_jpeg_decode_prog_u8`` call those of the progressive ones) and one ``io_png_decode`` call the slot of every referenced PNG image, then ``io_pair_planes_u8_hw`` runs on the arena as it does for dense arrays.  (A batch without polygons,
         JPEG or PNG images has empty regions for them: the layout of the run-length path as it was.)"""
         from . import jpeg, png, poly, rle
         P = len(items)
@@ -240,7 +240,11 @@ class PairRenderer(object):
         # an instance of the decoded region is a run-length code (of RLEMasks, or one inside PolyMasks) or a polygon
         refs = [(key, (masks[key[1]], key[2]) if isinstance(masks[key[1]], rle.RLEMasks) else masks[key[1]].rle_ref(key[2]))
                 for key in dec if key[0] == "m"]
-        jp_keys = [key for key in dec if key[0] == "img" and is_jpeg(images[key[1]])]
+        jp_keys = [key for key in dec if key[0] == "img" and is_jpeg(images[key[1]]) and not images[key[1]].progressive]
+        # progressive files: a second descriptor group, workspace and launch (io_jpeg_decode_prog_u8) behind the baseline one
+        pj_keys = [key for key in dec if key[0] == "img" and is_jpeg(images[key[1]]) and images[key[1]].progressive]
+        pj = jpeg.descriptors_progressive([images[k[1]] for k in pj_keys], [0] * len(pj_keys)) if pj_keys else None
+        pj_blobs = jpeg.progressive_blobs(pj) if pj_keys else []     # views: the offsets set below are seen through them
         pg_keys = [key for key in dec if key[0] == "img" and is_png(images[key[1]])]
         gpool, gdesc = png.descriptors([images[k[1]] for k in pg_keys], [0] * len(pg_keys)) if pg_keys else (
             np.zeros(0, np.uint8), ())
@@ -264,7 +268,10 @@ class PairRenderer(object):
         jd_at = jt_at + (jtabs.size + 15) // 16 * 16
         gp_at = jd_at + (jdbytes + 15) // 16 * 16
         gd_at = gp_at + (gpool.size + 15) // 16 * 16
-        pd_at = gd_at + (gdbytes + 15) // 16 * 16
+        pj_at, pd_at = [], gd_at + (gdbytes + 15) // 16 * 16
+        for b in pj_blobs:
+            pj_at.append(pd_at)
+            pd_at += (b.size + 15) // 16 * 16
         dec_at = pd_at + (C.sizeof(desc) + 15) // 16 * 16             # = the bytes that are uploaded
         nbytes = dec_at + max(cursors[id(dec)], 16)
         ws_at = (nbytes + 15) // 16 * 16
@@ -277,6 +284,8 @@ class PairRenderer(object):
             jdesc[k].out_off = dec_at + dec[key]
         for k, key in enumerate(pg_keys):
             gdesc[k].out_off = dec_at + dec[key]
+        for k, key in enumerate(pj_keys):
+            pj["desc"][k].out_off = dec_at + dec[key]
         jws_at = (ws_at + ws_bytes + 15) // 16 * 16
         jent = jpeg.get_entropy()                                    # the stage jpeg.set_entropy names sizes the arena ...
         jws_bytes = jpeg.workspace_bytes(jdesc, jent) if jp_keys else 0
@@ -288,6 +297,11 @@ class PairRenderer(object):
         gst_at = gws_at + gws_bytes
         if pg_keys:
             end = gst_at + 4 * len(pg_keys)
+        pws_at = (end + 15) // 16 * 16
+        pws_bytes = jpeg.workspace_bytes_progressive(pj) if pj_keys else 0
+        pst_at = pws_at + pws_bytes
+        if pj_keys:
+            end = pst_at + 4 * len(pj_keys)
         for k, ((ii, i1, i2, box, interp, flip), (kimg, region, k1, k2)) in enumerate(zip(items, keys)):
             base = dec_at if region is dec else 0
             _, H, W = masks[ii].shape
@@ -310,13 +324,18 @@ class PairRenderer(object):
         if pg_keys:
             host[gp_at:gp_at + gpool.size] = gpool
             host[gd_at:gd_at + gdbytes] = np.frombuffer(gdesc, dtype=np.uint8)
+        for a, b in zip(pj_at, pj_blobs):
+            host[a:a + b.size] = b
         host[pd_at:pd_at + C.sizeof(desc)] = np.frombuffer(desc, dtype=np.uint8)
         dev = torch.empty(end, dtype=torch.uint8, device=self.device)
         dev[:dec_at].copy_(stage[:dec_at], non_blocking=True)
         stream = torch.cuda.current_stream(self.device)
         self._upload_done(slot, stream)
-        self.last_upload = dict(images=sent["img"] + jpool.size + jtabs.size + gpool.size, masks=sent["m"] + ends.nbytes + verts.nbytes,
-                                descriptors=C.sizeof(rdesc) + sum(pbytes) + jdbytes + gdbytes + C.sizeof(desc), total=dec_at)
+        pj_sent = [b.size for b in pj_blobs] or [0] * 6              # tables, huff, desc, image, scan, pool
+        self.last_upload = dict(images=sent["img"] + jpool.size + jtabs.size + gpool.size + pj_sent[0] + pj_sent[1] + pj_sent[5],
+                                masks=sent["m"] + ends.nbytes + verts.nbytes,
+                                descriptors=C.sizeof(rdesc) + sum(pbytes) + jdbytes + gdbytes + sum(pj_sent[2:5]) + C.sizeof(desc),
+                                total=dec_at)
         base = dev.data_ptr()
         if jp_keys:
             # ... and is the entry point called: io_jpeg_decode_u8 or io_jpeg_decode_par_u8
@@ -333,6 +352,13 @@ class PairRenderer(object):
             words = torch.empty(len(pg_keys), dtype=torch.int32).pin_memory()
             words.copy_(dev[gst_at:gst_at + 4 * len(pg_keys)].view(torch.int32), non_blocking=True)
             self._status[slot] = (self._status[slot] or []) + [(words, [images[k[1]] for k in pg_keys], png)]
+            self._upload_done(slot, stream)
+        if pj_keys:
+            jpeg.launch_progressive(pj, base + pj_at[5], base + pj_at[0], base + pj_at[1], base + pj_at[2], base + pj_at[3],
+                                    base + pj_at[4], base, nbytes, base + pws_at, pws_bytes, base + pst_at, stream.cuda_stream)
+            words = torch.empty(len(pj_keys), dtype=torch.int32).pin_memory()
+            words.copy_(dev[pst_at:pst_at + 4 * len(pj_keys)].view(torch.int32), non_blocking=True)
+            self._status[slot] = (self._status[slot] or []) + [(words, [images[k[1]] for k in pj_keys], jpeg)]
             self._upload_done(slot, stream)
         if dec_keys:
             rc = _lib.lib().io_rle_decode_u8(C.c_void_p(base + tab_at), C.c_size_t(ends.size), C.c_void_p(base + rd_at),

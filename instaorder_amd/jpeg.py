@@ -28,7 +28,13 @@ streams whose dequantised coefficients fit int16 (its SIMD path holds them in 16
 Step 1 has two implementations on the device with the same result: one lane per image (``io_jpeg_decode_u8``, the default)
 and the lanes of a workgroup on the subsequences of one image (``io_jpeg_decode_par_u8``, csrc/jpeg_sync.h), chosen by
 ``set_entropy``; ``JpegImage.parallel_plan`` is the rule of the latter in Python.
+
+Progressive files (SOF2) are refused by default ("not baseline: progressive DCT") and go to the loader's fallback.  With
+``set_progressive("device")``, ``JpegImage(..., progressive=True)`` or IO_JPEG_PROGRESSIVE=device the complete progressions of
+DESIGN.md "Progressive JPEG" are accepted: step 1 then fills the same coefficients over the file's scans by T.81 G.1.2
+(``JpegImage.scans``, ``scan_levels``; ``io_jpeg_decode_prog_u8``, csrc/jpeg_prog.h), steps 2 to 5 are unchanged.
 """
+import collections
 import ctypes as C
 import os
 import re
@@ -67,16 +73,26 @@ def _u16(b, p):
     return struct.unpack_from(">H", b, p)[0]
 
 
+# one scan of an accepted progressive file: component indices in frame order, Ss, Se, Ah, Al, [start, end) of its
+# entropy-coded segment in the file, the restart interval in effect, and per scan component the (16 counts, symbols) bytes of
+# the Huffman table in effect -- the DC table in a DC scan, the AC table in an AC scan, None in a DC refinement
+ProgScan = collections.namedtuple("ProgScan", "comps ss se ah al start end restart_interval tables")
+
+
 class JpegImage(object):
     """One JPEG file, parsed but not decoded.  Stands in for a uint8 [H, W, 3] array where the consumers only look at
     ``shape`` / ``dtype``; ``supported`` says whether the device decoder takes it (``reason`` why not)."""
     dtype = np.dtype(np.uint8)
     ndim = 3
 
-    def __init__(self, data, name=None):
+    def __init__(self, data, name=None, progressive=None):
         self.data = bytes(data)
         self.name = name if name is not None else "<%d bytes>" % len(self.data)
         self.reason = None
+        self.progressive = False        # an accepted SOF2 file: ``scans`` holds its scans
+        self.scans = []
+        self._scan_data = {}
+        self._want_progressive = (get_progressive() == "device") if progressive is None else bool(progressive)
         self.H = self.W = 0
         self.components = []            # (id, h, v, quant table) in frame order
         self.restart_interval = 0
@@ -123,6 +139,7 @@ class JpegImage(object):
         sof = None
         scans = 0
         scan_sel = None
+        prog, late_dqt = [], False      # every scan as (selectors, Ss, Se, Ah, Al, start, end, DRI, Huffman tables) in file order
         while True:
             if p >= n:
                 raise ValueError("JPEG %s: the file ends without an EOI marker" % self.name)
@@ -154,6 +171,7 @@ class JpegImage(object):
             elif m == 0xEE and s[:5] == b"Adobe" and len(s) >= 12:
                 adobe = s[11]
             elif m == 0xDB:
+                late_dqt = late_dqt or scans > 0
                 i = 0
                 while i < len(s):
                     pq, tq = s[i] >> 4, s[i] & 15
@@ -186,7 +204,7 @@ class JpegImage(object):
                 sof = m
                 precision, self.H, self.W = s[0], _u16(s, 1), _u16(s, 3)
                 self.components = [(s[6 + 3 * k], s[7 + 3 * k] >> 4, s[7 + 3 * k] & 15, s[8 + 3 * k]) for k in range(s[5])]
-                if m != 0xC0:
+                if m != 0xC0 and not (m == 0xC2 and self._want_progressive):
                     self._no("not baseline: " + _SOF_REASON.get(m, "frame type 0x%02x" % m))
                 elif precision != 8:
                     self._no("%d-bit samples" % precision)
@@ -211,8 +229,10 @@ class JpegImage(object):
                         q += 1
                     else:
                         break
+                ns = s[0]
+                prog.append(([(s[1 + 2 * k], s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(ns)], s[1 + 2 * ns],
+                             s[2 + 2 * ns], s[3 + 2 * ns] >> 4, s[3 + 2 * ns] & 15, start, q, self.restart_interval, dict(huff)))
                 if scans == 1:
-                    ns = s[0]
                     scan_sel = ([(s[1 + 2 * k], s[2 + 2 * k] >> 4, s[2 + 2 * k] & 15) for k in range(ns)],
                                 tuple(s[1 + 2 * ns:4 + 2 * ns]))
                     self.entropy = (start, q)
@@ -220,6 +240,11 @@ class JpegImage(object):
                 p = q
         if sof is None or scans == 0:
             raise ValueError("JPEG %s: no frame or no scan" % self.name)
+        if sof == 0xC2 and self._want_progressive:
+            self._tables = (self._tables[0], {})
+            if self.reason is None:
+                self._classify_progressive(prog, late_dqt, jfif, adobe)
+            return
         if scans > 1:
             self._no("%d scans" % scans)
         self._classify(scan_sel, jfif, adobe)
@@ -236,17 +261,7 @@ class JpegImage(object):
         if (ss, se, ahal) != (0, 63, 0):
             self._no("spectral selection / successive approximation in a sequential scan")
             return
-        if len(comps) == 3:
-            ids = bytes(c[0] for c in comps)
-            if not (jfif or (adobe is None and ids != b"RGB") or adobe == 1):
-                self._no("RGB colour space (Adobe transform %s)" % adobe)
-                return
-            samp = tuple((c[1], c[2]) for c in comps)
-            if samp[1:] != ((1, 1), (1, 1)) or samp[0] not in ((1, 1), (2, 1), (2, 2)):
-                self._no("sampling %s" % " ".join("%dx%d" % hv for hv in samp))
-                return
-        elif (comps[0][1], comps[0][2]) != (1, 1):
-            self._no("sampling %dx%d of a single component" % (comps[0][1], comps[0][2]))
+        if not self._classify_frame(jfif, adobe):
             return
         quant, huff = self._tables
         for (cid, h, v, tq), (_, td, ta) in zip(comps, sel):
@@ -259,6 +274,89 @@ class JpegImage(object):
             elif (0, td) not in huff or (1, ta) not in huff:
                 self._no("a Huffman table is missing")
         self.scan_tables = [(td, ta) for _, td, ta in sel]
+
+    def _classify_frame(self, jfif, adobe):
+        """the colour-space and sampling rules, the same for baseline and progressive files"""
+        comps = self.components
+        if len(comps) == 3:
+            ids = bytes(c[0] for c in comps)
+            if not (jfif or (adobe is None and ids != b"RGB") or adobe == 1):
+                self._no("RGB colour space (Adobe transform %s)" % adobe)
+                return False
+            samp = tuple((c[1], c[2]) for c in comps)
+            if samp[1:] != ((1, 1), (1, 1)) or samp[0] not in ((1, 1), (2, 1), (2, 2)):
+                self._no("sampling %s" % " ".join("%dx%d" % hv for hv in samp))
+                return False
+        elif (comps[0][1], comps[0][2]) != (1, 1):
+            self._no("sampling %dx%d of a single component" % (comps[0][1], comps[0][2]))
+            return False
+        return True
+
+    def _classify_progressive(self, prog, late_dqt, jfif, adobe):
+        """the rules of DESIGN.md "Progressive JPEG": which SOF2 files the device takes; fills ``scans``"""
+        comps = self.components
+        why = "progressive DCT: "
+        if len(comps) not in (1, 3):
+            return self._no(why + ("%d components (CMYK / YCCK)" % len(comps) if len(comps) == 4 else "%d components" % len(comps)))
+        if not self._classify_frame(jfif, adobe):
+            self.reason = why + self.reason
+            return
+        if late_dqt:
+            return self._no(why + "a quantisation table defined between scans")
+        quant = self._tables[0]
+        for cid, h, v, tq in comps:
+            if tq not in quant:
+                return self._no(why + "quantisation table %d is missing" % tq)
+            if quant[tq] is None:
+                return self._no(why + "16-bit quantisation table")
+        index = {c[0]: k for k, c in enumerate(comps)}
+        al_of = [[None] * 64 for _ in comps]                 # the Al every coefficient has been sent down to
+        out = []
+        for n, (sel, ss, se, ah, al, start, end, ri, huff) in enumerate(prog):
+            what = why + "scan %d " % n
+            cs = [index.get(cid, -1) for cid, td, ta in sel]
+            if not cs or min(cs) < 0 or cs != sorted(set(cs)):
+                return self._no(what + "does not name components of the frame in frame order")
+            if ss == 0:
+                if se != 0:
+                    return self._no(what + "mixes DC and AC coefficients (Ss 0, Se %d)" % se)
+                if len(cs) != 1 and len(cs) != len(comps):
+                    return self._no(what + "is a DC scan of %d of %d components" % (len(cs), len(comps)))
+            elif len(cs) != 1 or not 1 <= ss <= se <= 63:
+                return self._no(what + "is an AC scan of %d components with Ss %d, Se %d" % (len(cs), ss, se))
+            if al > 13:
+                return self._no(what + "has Al %d above 13" % al)
+            if ah != 0 and ah != al + 1:
+                return self._no(what + "refines by more than one bit (Ah %d, Al %d)" % (ah, al))
+            tabs = []
+            for c, (cid, td, ta) in zip(cs, sel):
+                if ss and al_of[c][0] is None:
+                    return self._no(what + "is an AC scan in front of the DC scan of its component")
+                have = set(al_of[c][ss:se + 1])
+                if ah == 0 and have != {None}:
+                    return self._no(what + "sends coefficients a second time")
+                if ah and have != {ah}:
+                    return self._no(what + "refines coefficients that are not at Al %d" % ah)
+                al_of[c][ss:se + 1] = [al] * (se + 1 - ss)
+                key = (1, ta) if ss else (0, td)
+                if ss == 0 and ah:
+                    tabs.append(None)                        # a DC refinement reads plain bits
+                elif key not in huff:
+                    return self._no(what + "names a Huffman table that is missing")
+                else:
+                    tabs.append((huff[key][0].tobytes(), huff[key][1].tobytes()))
+            out.append(ProgScan(tuple(cs), ss, se, ah, al, start, end, ri, tuple(tabs)))
+        for c in range(len(comps)):
+            if al_of[c][0] is None:
+                return self._no(why + "incomplete progression: no DC scan of component %d" % c)
+            if any(a != 0 for a in al_of[c]):
+                k = [a != 0 for a in al_of[c]].index(True)
+                return self._no(why + "incomplete progression: coefficient %d of component %d %s" % (
+                    k, c, "is never sent" if al_of[c][k] is None else "stops at Al %d" % al_of[c][k]))
+        self.scans = out
+        self.progressive = True
+        self.restart_interval = out[0].restart_interval
+        self.entropy = (out[0].start, out[-1].end)
 
     # ---- what the device reads ---------------------------------------------------------------------------------------
     @property
@@ -306,6 +404,8 @@ class JpegImage(object):
         stream the kernel would flag).  ``stats``: a dict that receives symbols (Huffman symbols decoded), zrl,
         max_code_length and max_dc_category."""
         self._require()
+        if self.progressive:
+            return self._coefficients_progressive(stats)
         st = dict(symbols=0, zrl=0, max_code_length=0, max_dc_category=0)
         quant, huff = self._tables
         hs, vs = self.luma_sampling
@@ -416,9 +516,192 @@ class JpegImage(object):
                 blk += 1
         return coef
 
+    # ---- progressive files: the scans, their levels and the rule of csrc/jpeg_prog.h in Python ------------------------------
+    def scan_bytes(self, index):
+        """the entropy-coded segment of scan ``index`` of a progressive file"""
+        if index in self._scan_data:
+            return self._scan_data[index]
+        return self.data[self.scans[index].start:self.scans[index].end]
+
+    def with_scan(self, index, data, name=None):
+        """``with_entropy`` for one scan of a progressive file"""
+        import copy
+        out = copy.copy(self)
+        out._scan_data = dict(self._scan_data)
+        out._scan_data[index] = bytes(data)
+        out.name = name if name is not None else self.name + " (scan %d altered)" % index
+        return out
+
+    def scan_levels(self):
+        """per scan: 1 + the highest level of an earlier scan that shares a (component, coefficient) pair with it, 0 if
+        there is none; an AC scan counts the first DC scan of its component among them, as the format orders the two (so
+        the levels follow the file's own order of dependence: Pillow's ten-scan colour script has four).  Scans of one
+        level touch disjoint coefficients, so the device runs them side by side."""
+        last, first_dc, levels = {}, {}, []
+        for sc in self.scans:
+            pairs = [(c, k) for c in sc.comps for k in range(sc.ss, sc.se + 1)]
+            lv = 1 + max([last.get(p, -1) for p in pairs] + [first_dc.get(c, -1) for c in sc.comps if sc.ss])
+            for p in pairs:
+                last[p] = lv
+            if sc.ss == 0:
+                for c in sc.comps:
+                    first_dc.setdefault(c, lv)
+            levels.append(lv)
+        return levels
+
+    def scan_blocks(self, index):
+        """(block index in the [n_blocks, 64] MCU-ordered buffer of every block of the scan in scan order, blocks per MCU
+        of the scan, blocks across, blocks down).  A scan of all components walks the MCUs; a scan of one component walks
+        that component's own ceil(w_c / 8) x ceil(h_c / 8) raster, an MCU being one block."""
+        sc = self.scans[index]
+        hs, vs = self.luma_sampling
+        nc = len(self.components)
+        mw, mh = -(-self.W // (8 * hs)), -(-self.H // (8 * vs))
+        luma = hs * vs
+        bpm = luma + (2 if nc == 3 else 0)
+        if len(sc.comps) > 1:
+            return np.arange(mw * mh * bpm), bpm, mw, mh
+        c = sc.comps[0]
+        ch, cv = (hs, vs) if c == 0 else (1, 1)
+        bw = -(-(-(-self.W * ch // hs)) // 8)
+        bh = -(-(-(-self.H * cv // vs)) // 8)
+        by, bx = np.mgrid[0:bh, 0:bw]
+        r = (by % cv) * ch + bx % ch if c == 0 else luma + c - 1
+        return (((by // cv) * mw + bx // ch) * bpm + r).reshape(-1), 1, bw, bh
+
+    def _coefficients_progressive(self, stats):
+        st = dict(symbols=0, zrl=0, max_code_length=0, max_dc_category=0, eobrun_max=0, eobrun_refine_max=0, zrl_refine=0,
+                  correction_bits=0, restarts=0)
+        if stats is not None:
+            stats.update(st)
+            st = stats
+        hs, vs = self.luma_sampling
+        mw, mh = -(-self.W // (8 * hs)), -(-self.H // (8 * vs))
+        bpm = hs * vs + (2 if len(self.components) == 3 else 0)
+        coef = np.zeros((mw * mh * bpm, 64), np.int64)
+        for n in range(len(self.scans)):
+            self._decode_scan(n, coef, st)
+        return coef.astype(np.int16)
+
+    def _decode_scan(self, index, coef, st):
+        """one scan by T.81 G.1.2 into ``coef`` (int64 [n_blocks, 64] holding int16 values)"""
+        sc = self.scans[index]
+        ss, se, ah, al = sc.ss, sc.se, sc.ah, sc.al
+        order, per_mcu, _, _ = self.scan_blocks(index)
+        luma = self.luma_sampling[0] * self.luma_sampling[1]
+        looks = [None if t is None else _lookup(t[0], t[1], self.name) for t in sc.tables]
+        bits = _Bits(self.scan_bytes(index), self.name)
+        zz = [int(v) for v in ZIGZAG]
+        p1, m1 = 1 << al, -1 << al
+
+        def symbol(tab):
+            c = bits.peek16()
+            l = int(tab[0][c])
+            if l == 0:
+                raise JpegStreamError(1, self.name)
+            bits.skip(l)
+            st["symbols"] += 1
+            st["max_code_length"] = max(st["max_code_length"], l)
+            return int(tab[1][c])
+
+        def wrap16(v):
+            return ((v + 0x8000) & 0xFFFF) - 0x8000
+
+        pred = [0, 0, 0]
+        eobrun = 0
+        n_mcu = len(order) // per_mcu
+        for mcu in range(n_mcu):
+            if sc.restart_interval and mcu and mcu % sc.restart_interval == 0:
+                bits.restart()
+                st["restarts"] += 1
+                pred = [0, 0, 0]
+                eobrun = 0
+            for r in range(per_mcu):
+                blk = coef[int(order[mcu * per_mcu + r])]
+                j = 0 if per_mcu == 1 else (0 if r < luma else 1 + r - luma)      # which of the scan's components
+                if ss == 0 and ah == 0:                          # DC first
+                    t = symbol(looks[j])
+                    if t > 15:
+                        raise JpegStreamError(5, self.name)
+                    st["max_dc_category"] = max(st["max_dc_category"], t)
+                    if t:
+                        pred[j] += bits.receive_extend(t)
+                    blk[0] = wrap16(pred[j] << al)
+                elif ss == 0:                                    # DC refinement
+                    if bits.take(1):
+                        blk[0] = wrap16(int(blk[0]) | p1)
+                elif ah == 0:                                    # AC first
+                    if eobrun > 0:
+                        eobrun -= 1
+                        continue
+                    k = ss
+                    while k <= se:
+                        rs = symbol(looks[0])
+                        run, size = rs >> 4, rs & 15
+                        if size:
+                            k += run
+                            if k > se:
+                                raise JpegStreamError(2, self.name)
+                            blk[zz[k]] = wrap16(bits.receive_extend(size) << al)
+                            k += 1
+                        elif run == 15:
+                            st["zrl"] += 1
+                            k += 16
+                            if k > se + 1:
+                                raise JpegStreamError(2, self.name)
+                        else:
+                            eobrun = (1 << run) + (bits.take(run) if run else 0)
+                            st["eobrun_max"] = max(st["eobrun_max"], eobrun)
+                            eobrun -= 1
+                            break
+                else:                                            # AC refinement
+                    k = ss
+                    if eobrun == 0:
+                        while k <= se:
+                            rs = symbol(looks[0])
+                            run, size = rs >> 4, rs & 15
+                            value = 0
+                            if size:
+                                if size != 1:
+                                    raise JpegStreamError(1, self.name)
+                                value = p1 if bits.take(1) else m1
+                            elif run != 15:
+                                eobrun = (1 << run) + (bits.take(run) if run else 0)
+                                st["eobrun_refine_max"] = max(st["eobrun_refine_max"], eobrun)
+                                break
+                            else:
+                                st["zrl_refine"] += 1
+                            while k <= se:                       # over the coefficients that are known, and `run` that are not
+                                v = int(blk[zz[k]])
+                                if v:
+                                    st["correction_bits"] += 1
+                                    if bits.take(1) and not v & p1:
+                                        blk[zz[k]] = wrap16(v + (p1 if v > 0 else m1))
+                                else:
+                                    run -= 1
+                                    if run < 0:
+                                        break
+                                k += 1
+                            if value:
+                                if k > se:
+                                    raise JpegStreamError(2, self.name)
+                                blk[zz[k]] = wrap16(value)
+                            k += 1
+                    if eobrun > 0:
+                        while k <= se:
+                            v = int(blk[zz[k]])
+                            if v:
+                                st["correction_bits"] += 1
+                                if bits.take(1) and not v & p1:
+                                    blk[zz[k]] = wrap16(v + (p1 if v > 0 else m1))
+                            k += 1
+                        eobrun -= 1
+
     # ---- the parallel entropy stage in Python (csrc/jpeg_sync.h) ---------------------------------------------------------
     def _sync_context(self):
         self._require()
+        if self.progressive:
+            raise ValueError("JPEG image %s is progressive: the parallel entropy stage decodes baseline scans" % self.name)
         _, huff = self._tables
         hs, vs = self.luma_sampling
         nc = len(self.components)
@@ -710,6 +993,76 @@ class JpegImage(object):
         return np.clip(np.stack([R, G, B], 2), 0, 255).astype(np.uint8)
 
 
+def _lookup(counts, symbols, name):
+    """16-bit prefix -> (code length or 0, symbol) of one Huffman table given as the bytes of its DHT entry"""
+    ln = np.zeros(1 << 16, np.uint8)
+    sv = np.zeros(1 << 16, np.uint8)
+    code, k = 0, 0
+    for l in range(1, 17):
+        for _ in range(counts[l - 1]):
+            if code >= 1 << l:
+                raise ValueError("JPEG %s: Huffman code lengths that form no prefix code" % name)
+            lo = code << (16 - l)
+            ln[lo:lo + (1 << (16 - l))] = l
+            sv[lo:lo + (1 << (16 - l))] = symbols[k]
+            code += 1
+            k += 1
+        code <<= 1
+    return ln, sv
+
+
+class _Bits(object):
+    """the bits of one entropy-coded segment: FF fill bytes dropped, FF 00 unstuffed, split at the restart markers; inside
+    an interval the reader stops at any other marker.  Raises the JpegStreamError the kernel's status word stands for."""
+
+    def __init__(self, raw, name):
+        self.name = name
+        raw = _FILL.sub(b"", raw)
+        segs, self.marks, at = [], [], 0
+        for mt in _RST.finditer(raw):
+            segs.append(raw[at:mt.start()])
+            self.marks.append(raw[mt.end() - 1] - 0xD0)
+            at = mt.end()
+        segs.append(raw[at:])
+        self.clean, self.cut = [], []
+        for sg in segs:
+            mt = _MARKER.search(sg)
+            self.cut.append(mt is not None)
+            if mt:
+                sg = sg[:mt.start()]
+            self.clean.append(sg.replace(b"\xff\x00", b"\xff"))
+        self.seg = -1
+        self._enter(0)
+
+    def _enter(self, k):
+        self.seg, self.buf, self.bits, self.pos = k, self.clean[k] + b"\0" * 8, 8 * len(self.clean[k]), 0
+
+    def peek16(self):
+        p = self.pos
+        return (int.from_bytes(self.buf[p >> 3:(p >> 3) + 4], "big") >> (16 - (p & 7))) & 0xFFFF
+
+    def skip(self, k):
+        self.pos += k
+        if self.pos > self.bits:
+            raise JpegStreamError(4, self.name)
+
+    def take(self, s):
+        """the next s bits (1 <= s <= 15) as an unsigned number"""
+        v = self.peek16() >> (16 - s)
+        self.skip(s)
+        return v
+
+    def receive_extend(self, s):
+        v = self.take(s)
+        return v if v >= 1 << (s - 1) else v - (1 << s) + 1
+
+    def restart(self):
+        k = self.seg
+        if self.bits - self.pos >= 8 or self.cut[k] or k >= len(self.marks) or self.marks[k] != k % 8:
+            raise JpegStreamError(3, self.name)
+        self._enter(k + 1)
+
+
 def _idct8(i0, i1, i2, i3, i4, i5, i6, i7):
     """one 8-point pass of jidctint.c on int32 arrays, without the descale"""
     z1 = (i2 + i6) * 4433
@@ -794,6 +1147,81 @@ def descriptors(images, out_offs):
     return pool, tables, desc
 
 
+def descriptors_progressive(images, out_offs):
+    """dict(pool, tables, huff, desc, image, scan) for a list of accepted progressive ``JpegImage`` and the byte offset of
+    each decoded image: what ``io_jpeg_decode_prog_u8`` reads.  pool: the entropy-coded bytes of all scans; tables: uint8
+    [n_sets * 1600], the quantisation tables (identical sets stored once); huff: uint8 [n_huff * 272], the raw Huffman
+    tables (identical tables stored once); desc / image / scan: the JpegDesc, JpegProgImage and JpegProgScan arrays."""
+    n_scans = sum(len(im.scans) for im in images)
+    desc = (_lib.JpegDesc * len(images))()
+    recs = (_lib.JpegProgImage * len(images))()
+    scans = (_lib.JpegProgScan * max(n_scans, 1))()
+    sets, blobs, tabs, chunks, cursor, g = {}, [], {}, [], 0, 0
+    for k, (im, o) in enumerate(zip(images, out_offs)):
+        im._require()
+        if not im.progressive:
+            raise ValueError("jpeg.descriptors_progressive: %s is a baseline file" % im.name)
+        blob = im.tables_blob()
+        if blob not in sets:
+            sets[blob] = len(blobs)
+            blobs.append(blob)
+        d = desc[k]
+        d.out_off, d.H, d.W, d.n_comp = int(o), im.H, im.W, len(im.components)
+        d.hs, d.vs = im.luma_sampling
+        d.table_set = sets[blob]
+        for c, (cid, h, v, tq) in enumerate(im.components):
+            d.quant[c] = tq
+        levels = im.scan_levels()
+        recs[k].first_scan, recs[k].n_scans, recs[k].n_levels = g, len(im.scans), max(levels) + 1
+        for n, (sc, lv) in enumerate(zip(im.scans, levels)):
+            s = scans[g]
+            ent = im.scan_bytes(n)
+            s.data_off, s.data_bytes, s.image, s.restart_interval, s.level = cursor, len(ent), k, sc.restart_interval, lv
+            s.n_comp, s.ss, s.se, s.ah, s.al = len(sc.comps), sc.ss, sc.se, sc.ah, sc.al
+            for j, (c, t) in enumerate(zip(sc.comps, sc.tables)):
+                s.comp[j] = c
+                if t is not None:
+                    s.table[j] = tabs.setdefault(t, len(tabs))
+            chunks.append(ent)
+            cursor += len(ent)
+            g += 1
+    pool = np.frombuffer(b"".join(chunks), np.uint8) if cursor else np.zeros(0, np.uint8)
+    huff = np.zeros((max(len(tabs), 1), 272), np.uint8)
+    for (cnt, sy), t in tabs.items():
+        huff[t, :16] = np.frombuffer(cnt, np.uint8)
+        huff[t, 16:16 + len(sy)] = np.frombuffer(sy, np.uint8)
+    return dict(pool=pool, tables=np.frombuffer(b"".join(blobs), np.uint8), huff=huff.reshape(-1), desc=desc, image=recs,
+                scan=scans, n_scans=n_scans)
+
+
+def workspace_bytes_progressive(p):
+    """bytes of workspace ``io_jpeg_decode_prog_u8`` needs for the tables of ``descriptors_progressive``"""
+    b = int(_lib.lib().io_jpeg_prog_workspace_bytes(C.cast(p["desc"], C.c_void_p), len(p["desc"]), p["huff"].size // 272,
+                                                    p["n_scans"]))
+    if b == 0:
+        raise RuntimeError("instaorder_hip io_jpeg_prog_workspace_bytes refused the descriptors: %s" % _lib.last_error())
+    return b
+
+
+def launch_progressive(p, pool, tables_dev, huff_dev, desc_dev, image_dev, scan_dev, out, out_bytes, ws, ws_bytes, status,
+                       stream, concurrent=None):
+    """one ``io_jpeg_decode_prog_u8`` call for the tables ``p`` of ``descriptors_progressive``; device addresses as ints"""
+    concurrent = _PROGRESSIVE["concurrent"] if concurrent is None else int(concurrent)
+    rc = _lib.lib().io_jpeg_decode_prog_u8(
+        C.c_void_p(pool), C.c_size_t(p["pool"].size), C.c_void_p(tables_dev), p["tables"].ctypes.data_as(C.c_void_p),
+        C.c_size_t(p["tables"].size), C.c_void_p(huff_dev), p["huff"].ctypes.data_as(C.c_void_p), p["huff"].size // 272,
+        C.c_void_p(desc_dev), C.cast(p["desc"], C.c_void_p), C.c_void_p(image_dev), C.cast(p["image"], C.c_void_p),
+        len(p["desc"]), C.c_void_p(scan_dev), C.cast(p["scan"], C.c_void_p), p["n_scans"], C.c_void_p(out),
+        C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status), concurrent, C.c_void_p(stream))
+    _lib.check(rc, "io_jpeg_decode_prog_u8")
+
+
+def progressive_blobs(p):
+    """the uint8 arrays of ``p`` that travel to the device, in the order (tables, huff, desc, image, scan, pool)"""
+    return [p["tables"], p["huff"], np.frombuffer(p["desc"], dtype=np.uint8), np.frombuffer(p["image"], dtype=np.uint8),
+            np.frombuffer(p["scan"], dtype=np.uint8), p["pool"]]
+
+
 # ---- which entropy stage the device decoder runs --------------------------------------------------------------------------
 _ENTROPY = dict(mode="sequential", subseq_bytes=256, max_rounds=64)
 
@@ -828,6 +1256,33 @@ def get_entropy(entropy=None):
 
 if os.environ.get("IO_JPEG_ENTROPY", ""):
     set_entropy(os.environ["IO_JPEG_ENTROPY"])
+
+
+# ---- who decodes a progressive file -----------------------------------------------------------------------------------------
+_PROGRESSIVE = dict(mode="host", concurrent=1)
+
+
+def set_progressive(mode, concurrent=1):
+    """Who decodes a progressive (SOF2) file: "host" -- ``JpegImage.supported`` is False with "progressive" in its reason
+    and ``loader`` hands the file to its fallback, the default -- or "device": ``JpegImage`` accepts the progressive files
+    of DESIGN.md "Progressive JPEG" and ``io_jpeg_decode_prog_u8`` decodes them.  ``concurrent`` (1 or 0): the scans of one
+    level side by side on the waves of a block, or all scans in file order on one lane; pixels and status words do not
+    depend on it.  Module-wide; applies to ``JpegImage`` objects made afterwards.  The environment variable
+    IO_JPEG_PROGRESSIVE=device selects the device at import; any other non-empty value of it raises this function's
+    ValueError when ``instaorder_amd.jpeg`` is imported."""
+    if mode not in ("host", "device"):
+        raise ValueError("jpeg.set_progressive: mode %r ('host' or 'device')" % (mode,))
+    if concurrent not in (0, 1):
+        raise ValueError("jpeg.set_progressive: concurrent %r (0 or 1)" % (concurrent,))
+    _PROGRESSIVE.update(mode=mode, concurrent=int(concurrent))
+
+
+def get_progressive():
+    return _PROGRESSIVE["mode"]
+
+
+if os.environ.get("IO_JPEG_PROGRESSIVE", ""):
+    set_progressive(os.environ["IO_JPEG_PROGRESSIVE"])
 
 
 def workspace_bytes(desc, entropy=None):
@@ -868,12 +1323,14 @@ def raise_for_status(status, images):
                                                                for nm, s in bad))
 
 
-def decode(images, device, out=None, entropy=None, info=False):
+def decode(images, device, out=None, entropy=None, info=False, concurrent=None):
     """list of supported ``JpegImage`` -> list of uint8 [H, W, 3] device tensors through one ``io_jpeg_decode_u8`` call on
     the current stream (views of ``out``, a contiguous uint8 device tensor of at least the summed sizes, when given).
     Waits for the status words and raises RuntimeError naming the images that did not decode.  ``entropy``: "sequential"
     or "parallel" instead of the ``set_entropy`` mode.  With ``info`` the result is (tensors, int32 array): the info word
-    of every image (``JpegImage.parallel_plan``; zeros from the sequential stage)."""
+    of every image (``JpegImage.parallel_plan``; zeros from the sequential stage).  Baseline and accepted progressive
+    images may be mixed: the baseline ones go through that call, the progressive ones through one ``io_jpeg_decode_prog_u8``
+    call (``concurrent``: 1 or 0 instead of the ``set_progressive`` value) into the same output and one status vector."""
     import torch
     _lib.require_gpu()
     device = torch.device(device)
@@ -895,8 +1352,15 @@ def decode(images, device, out=None, entropy=None, info=False):
     elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < total:
         raise ValueError("jpeg.decode: out must be a contiguous uint8 device tensor of at least %d bytes" % total)
     out = out.view(-1)
-    pool, tables, desc = descriptors(images, offs)
-    blobs = [tables, np.frombuffer(desc, dtype=np.uint8), pool]
+    base_idx = [k for k, im in enumerate(images) if not im.progressive]
+    prog_idx = [k for k, im in enumerate(images) if im.progressive]
+    blobs = []
+    if base_idx:
+        pool, tables, desc = descriptors([images[k] for k in base_idx], [offs[k] for k in base_idx])
+        blobs += [tables, np.frombuffer(desc, dtype=np.uint8), pool]
+    if prog_idx:
+        prog = descriptors_progressive([images[k] for k in prog_idx], [offs[k] for k in prog_idx])
+        blobs += progressive_blobs(prog)
     at, cursor = [], 0
     for b in blobs:
         at.append(cursor)
@@ -905,13 +1369,25 @@ def decode(images, device, out=None, entropy=None, info=False):
     for a, b in zip(at, blobs):
         host[a:a + b.size] = b
     dev = torch.from_numpy(host).to(out.device)
-    ws = torch.empty(workspace_bytes(desc, setting), dtype=torch.uint8, device=out.device)
+    # one status vector: the words of the baseline images, then those of the progressive ones
     status = torch.empty(len(images), dtype=torch.int32, device=out.device)
     words = torch.zeros(len(images), dtype=torch.int32, device=out.device)
     base = dev.data_ptr()
-    launch(setting, base + at[2], pool.size, base + at[0], tables, base + at[1], desc, out.data_ptr(), out.numel(),
-           ws.data_ptr(), ws.numel(), status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream,
-           info=words.data_ptr() if info else None)
+    stream = torch.cuda.current_stream(out.device).cuda_stream
+    if base_idx:
+        ws = torch.empty(workspace_bytes(desc, setting), dtype=torch.uint8, device=out.device)
+        launch(setting, base + at[2], pool.size, base + at[0], tables, base + at[1], desc, out.data_ptr(), out.numel(),
+               ws.data_ptr(), ws.numel(), status.data_ptr(), stream, info=words.data_ptr() if info else None)
+    if prog_idx:
+        a = at[3:] if base_idx else at
+        pws = torch.empty(workspace_bytes_progressive(prog), dtype=torch.uint8, device=out.device)
+        launch_progressive(prog, base + a[5], base + a[0], base + a[1], base + a[2], base + a[3], base + a[4], out.data_ptr(),
+                           out.numel(), pws.data_ptr(), pws.numel(), status.data_ptr() + 4 * len(base_idx), stream,
+                           concurrent=concurrent)
+    order = base_idx + prog_idx
+    if prog_idx and base_idx:
+        back = torch.from_numpy(np.argsort(order))
+        status, words = status.cpu()[back], words.cpu()[back]
     raise_for_status(status.cpu().numpy(), images)
     res = [out[o:o + s].view(im.H, im.W, 3) for o, s, im in zip(offs, sizes, images)]
     return (res, words.cpu().numpy()) if info else res
@@ -926,9 +1402,10 @@ def _pil_rgb(path):
     return np.array(Image.open(path).convert("RGB"))
 
 
-def loader(image_root, fallback=None):
+def loader(image_root, fallback=None, progressive=None):
     """``load_image(image_fn)`` for the dataset classes: a ``JpegImage`` for a file the device decodes, otherwise
-    ``fallback(path)`` -- by default the reference's own ``np.array(Image.open(path).convert('RGB'))``."""
+    ``fallback(path)`` -- by default the reference's own ``np.array(Image.open(path).convert('RGB'))``.  ``progressive``:
+    True / False, whether progressive files go to the device; None: as ``set_progressive`` says when a file is loaded."""
     fallback = _pil_rgb if fallback is None else fallback
 
     def load_image(image_fn):
@@ -937,7 +1414,7 @@ def loader(image_root, fallback=None):
             data = f.read()
         if data[:2] == b"\xff\xd8":
             try:
-                im = JpegImage(data, name=str(image_fn))
+                im = JpegImage(data, name=str(image_fn), progressive=progressive)
             except ValueError:
                 im = None
             if im is not None and im.supported:

@@ -999,10 +999,10 @@ def _pil_rgb(path):
     return np.array(Image.open(path).convert("RGB"))
 
 
-def loader(image_root, jpeg=True, fallback=None):
+def loader(image_root, jpeg=True, fallback=None, progressive=None):
     """``load_image(image_fn)`` for the dataset classes: a ``PngImage`` for a PNG file in a supported 8-bit form, with
-    ``jpeg`` a ``jpeg.JpegImage`` for a baseline JPEG file the device decodes, otherwise ``fallback(path)`` -- by default
-    the reference's own ``np.array(Image.open(path).convert('RGB'))``."""
+    ``jpeg`` a ``jpeg.JpegImage`` for a JPEG file the device decodes (``progressive`` as in ``jpeg.loader``), otherwise
+    ``fallback(path)`` -- by default the reference's own ``np.array(Image.open(path).convert('RGB'))``."""
     fallback = _pil_rgb if fallback is None else fallback
 
     def load_image(image_fn):
@@ -1017,7 +1017,7 @@ def loader(image_root, jpeg=True, fallback=None):
                     im = None
             elif jpeg and data[:2] == b"\xff\xd8":
                 from .jpeg import JpegImage
-                im = JpegImage(data, name=str(image_fn))
+                im = JpegImage(data, name=str(image_fn), progressive=progressive)
         except ValueError:
             im = None
         if im is not None and im.supported:

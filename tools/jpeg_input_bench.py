@@ -25,6 +25,15 @@ class of both stages with subsequences of 64, 128, 256, 512 and 1024 bytes.  The
 equal bit for bit.  No threshold: a ratio below 1 is reported as it is.
 
     python tools/jpeg_input_bench.py --parallel [--repeats 3] [--subseq-bytes 256] [--max-rounds 64] --out profiles/jpeg_parallel_bench.json
+
+With ``--progressive`` the two file sets are encoded with ``progressive=True`` instead and three legs alternate per set,
+``--repeats`` times each: "PIL in load_image" -- what becomes of such files without ``jpeg.set_progressive("device")``, so the
+baseline --, "JpegImage, progressive stage, scans in file order on one lane" (concurrent 0) and "..., scans of a level side by
+side" (concurrent 1), both through io_jpeg_decode_prog_u8.  Per leg the batch interval, the jpeg_prog_entropy class time, the
+upload bytes by kind and the cycles per Huffman symbol of that class are recorded, per set their median and spread.  The first
+batches of a set's legs must be equal bit for bit.  No threshold: a ratio below 1 is reported as it is.
+
+    python tools/jpeg_input_bench.py --progressive [--repeats 3] --out profiles/jpeg_progressive_bench.json
 """
 import argparse
 import io
@@ -203,8 +212,52 @@ def parallel_bench(rd, sets, a):
     return out, same
 
 
-def symbols_per_pixel(blobs):
-    ims = [jpeg.JpegImage(b) for b in blobs]
+def progressive_bench(rd, sets, a, clock_mhz):
+    """Pillow in load_image against the progressive stage with concurrent 0 and 1, per file set: the three legs alternating,
+    --repeats times each.  No threshold; the first batches must be equal."""
+    legs_of = (("PIL in load_image", "pil", None), ("JpegImage, progressive stage, scans in file order on one lane", "jpeg", 0),
+               ("JpegImage, progressive stage, scans of a level side by side", "jpeg", 1))
+    out, same = [], True
+    for set_name, files, sym_per_pixel, pixels in sets:
+        runs = {name: [] for name, _, _ in legs_of}
+        firsts = []
+        try:
+            for rep in range(a.repeats):
+                for name, how, concurrent in legs_of:
+                    jpeg.set_progressive("host" if concurrent is None else "device", concurrent or 0)
+                    res, first = run_leg("%s (%s, repeat %d)" % (name, set_name, rep), rd, files, how, a)
+                    ms = res["kernels"].get("jpeg_prog_entropy", {}).get("ms_per_batch")
+                    runs[name].append(dict(batch_ms_median=res["batch_ms_median"], batch_ms_mean=res["batch_ms_mean"],
+                                           batch_ms_min_max=res["batch_ms_min_max"], jpeg_prog_entropy_ms=ms,
+                                           load_image_ms_per_batch=res["load_image_ms_per_batch"],
+                                           upload_bytes_per_batch=res["upload_bytes_per_batch"],
+                                           # one block per image, all at once: the class lasts as long as an image's scans do
+                                           cycles_per_symbol=None if ms is None else round(
+                                               ms * 1e-3 * clock_mhz * 1e6 / (sym_per_pixel * pixels), 1)))
+                    firsts.append(first)
+        finally:
+            jpeg.set_progressive("host")
+        same = same and all(np.array_equal(x, y) for f in firsts[1:] for x, y in zip(firsts[0], f))
+
+        def spread(name, key):
+            v = [r[key] for r in runs[name] if r[key] is not None]
+            return dict(median=round(float(np.median(v)), 3), min=round(min(v), 3), max=round(max(v), 3)) if v else None
+
+        summary = {name: dict(batch_ms_median=spread(name, "batch_ms_median"), jpeg_prog_entropy_ms=spread(name, "jpeg_prog_entropy_ms"),
+                              cycles_per_symbol=spread(name, "cycles_per_symbol")) for name in runs}
+        pil = summary[legs_of[0][0]]["batch_ms_median"]["median"]
+        out.append(dict(files=set_name, file_bytes_mean=round(float(np.mean([len(b) for b in files.values()])), 1),
+                        pixel_bytes_mean=round(3 * pixels, 1), huffman_symbols_per_pixel=round(sym_per_pixel, 3), legs=runs,
+                        summary=summary,
+                        pil_over_one_lane_batch=round(pil / summary[legs_of[1][0]]["batch_ms_median"]["median"], 3),
+                        pil_over_side_by_side_batch=round(pil / summary[legs_of[2][0]]["batch_ms_median"]["median"], 3),
+                        one_lane_over_side_by_side_entropy=round(summary[legs_of[1][0]]["jpeg_prog_entropy_ms"]["median"] /
+                                                                 summary[legs_of[2][0]]["jpeg_prog_entropy_ms"]["median"], 3)))
+    return out, same
+
+
+def symbols_per_pixel(blobs, progressive=None):
+    ims = [jpeg.JpegImage(b, progressive=progressive) for b in blobs]
     stats = [{} for _ in ims]
     for im, st in zip(ims, stats):
         im.coefficients(st)
@@ -221,6 +274,8 @@ def main(argv=None):
     ap.add_argument("--out", default="")
     ap.add_argument("--parallel", action="store_true",
                     help="compare the sequential and the parallel entropy stage instead of the three legs (profiles/jpeg_parallel_bench.json)")
+    ap.add_argument("--progressive", action="store_true",
+                    help="Pillow against the progressive stage on progressive files instead (profiles/jpeg_progressive_bench.json)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--subseq-bytes", type=int, default=256)
     ap.add_argument("--max-rounds", type=int, default=64)
@@ -235,6 +290,40 @@ def main(argv=None):
         bio = io.BytesIO()
         Image.fromarray(sc["image"]).save(bio, "JPEG", quality=90, subsampling=2)
         files[rd.get_image_instances(i)[4]] = bio.getvalue()
+    if a.progressive:
+        sets = []
+        for set_name, picture in (("uniform noise", lambda i, sc: sc["image"]),
+                                  ("smooth picture with noise (sigma %g)" % SMOOTH_SIGMA,
+                                   lambda i, sc: smooth_picture(sc["image"].shape[0], sc["image"].shape[1], 9000 + i))):
+            prog = {}
+            for i, sc in enumerate(rd.scenes):
+                bio = io.BytesIO()
+                Image.fromarray(picture(i, sc)).save(bio, "JPEG", quality=90, subsampling=2, progressive=True)
+                prog[rd.get_image_instances(i)[4]] = bio.getvalue()
+            sets.append((set_name, prog, symbols_per_pixel(list(prog.values())[:1], progressive=True),
+                         float(np.mean([sc["image"].shape[0] * sc["image"].shape[1] for sc in rd.scenes]))))
+        props = torch.cuda.get_device_properties(0)
+        clock_mhz = props.clock_rate / 1e3 if hasattr(props, "clock_rate") else 2400.0
+        results, same = progressive_bench(rd, sets, a, clock_mhz)
+        res = dict(tool="tools/jpeg_input_bench.py --progressive", device=torch.cuda.get_device_name(0),
+                   csrc_digest=_lib.csrc_digest(), B=a.B, S=a.S, batches=a.batches, warmup=a.warmup, probe_batches=a.probe,
+                   repeats=a.repeats, libjpeg=str(features.version("jpg")), shader_clock_mhz=clock_mhz,
+                   reader="SyntheticReader(500, n_images=32, n_inst=8, max_side=640, min_side=480, empty_every=0), run-length "
+                          "masks, a new mask object (so an image load and upload) per item; both file sets progressive 4:2:0, "
+                          "quality 90, encoded once with Pillow (its ten-scan script); every image of a batch is progressive",
+                   first_batch_equal=bool(same), sets=results,
+                   samples="one timed leg of --batches batches per repeat, the three legs alternating; summary = median / min / "
+                           "max over the repeats; the symbol count is that of one file of the set, scaled by the pixels",
+                   not_measured="real COCO files; batches that mix progressive and baseline files; the pipeline beside a network "
+                                "step; a multi-threaded host decoder; the shader clock during the run (cycles assume the value given)")
+        print(json.dumps({k: v for k, v in res.items() if k != "sets"}), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+                f.write("\n")
+        if not same:
+            print("FAILED: the first batch of the legs differs")
+        return 0 if same else 1
     if a.parallel:
         smooth = {}
         for i, sc in enumerate(rd.scenes):
