@@ -260,6 +260,21 @@ int io_net_forward(io_net* net, const float* params, float* running, const void*
 size_t io_net_workspace_bytes_hw(const io_net* net, int N, int H, int W);
 int io_net_forward_eval_hw(io_net* net, const float* params, float* running, const void* x8, int N, int H, int W,
                            void* workspace, size_t workspace_bytes, float* logits, hipStream_t stream);
+/* The same forward with every unit it produces copied out, for unit-wise parity checks (the eval plan rotates six
+ * buffers, so only the last block survives a plain call).  Units in execution order, NHWC in the net's storage type,
+ * packed back to back: 0 relu(conv1 + b) [N,H/2,W/2,64], 1 max-pool [N,H/4,W/4,64], then per bottleneck a1 =
+ * relu(bn1(conv1)), a2 = relu(bn2(conv2)), yd = bn(downsample conv) where the block has that branch, out: 54 in all.
+ * taps (device, io_net_eval_taps_bytes) may be NULL; with it one device-to-device copy follows each unit on `stream`.
+ * routes (HOST int32[max_routes >= 53]) may be NULL; with it io_debug_last_nt_route() is recorded after each of the 53
+ * convolution launches (stem, then per block conv1, conv2, downsample, conv3).  The launches, the workspace and the
+ * logits are those of io_net_forward_eval_hw / io_net_forward(training = 0).
+ * io_net_eval_tap_offset: byte offset of unit `which` in the tap buffer, -1 on a bad shape or index;
+ * io_net_eval_taps_bytes: size of the tap buffer, 0 on a bad shape. */
+size_t io_net_eval_taps_bytes(const io_net* net, int N, int H, int W);
+long io_net_eval_tap_offset(const io_net* net, int N, int H, int W, int which);
+int io_net_forward_eval_taps(io_net* net, const float* params, float* running, const void* x8, int N, int H, int W,
+                             void* workspace, size_t workspace_bytes, float* logits, void* taps, size_t taps_bytes,
+                             int32_t* routes, int max_routes, hipStream_t stream);
 /* gradient of every parameter into grads (same layout as params; fully overwritten).  Must follow a
  * training io_net_forward with the same x8 / N / S / G / workspace. */
 

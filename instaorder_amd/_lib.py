@@ -196,6 +196,10 @@ SIGNATURES = {
     "io_net_workspace_bytes": (_Z, [_P, _I, _I, _I]),
     "io_net_workspace_bytes_hw": (_Z, [_P, _I, _I, _I]),
     "io_net_forward_eval_hw": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P, _P]),
+    "io_net_eval_taps_bytes": (_Z, [_P, _I, _I, _I]),
+    "io_net_eval_tap_offset": (_L, [_P, _I, _I, _I, _I]),
+    # net, params, running, x8, N, H, W, workspace, workspace_bytes, logits, taps, taps_bytes, routes (host int32), max_routes, stream
+    "io_net_forward_eval_taps": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P, _P, _Z, C.POINTER(C.c_int32), _I, _P]),
     "io_net_activation_offset": (_L, [_P, _I, _I, _I]),
     "io_net_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P, _P]),
     "io_net_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),

@@ -562,10 +562,68 @@ int conv_folded(const Ctx& c, const ConvL& L, const BnL& b, const void* x, void*
                              c.dt(), c.dt());
 }
 
-int run_forward_eval(Ctx& c, const void* x8, float* logits) {
+// ---- eval taps (tests): every unit an inference forward produces, copied out of the six rotating buffers ---------------
+// Units in execution order: relu(conv1 + b), max-pool, then per block a1, a2, (yd where the block has a downsample
+// branch), out -- 2 + 16 * 3 + 4 = 54.  Packed back to back: every unit is N * H * W * C elements with 64 | C, so every
+// offset is a multiple of 128 bytes without padding and the sizes sum to the byte count.
+constexpr int kEvalConvs = 53;      // conv_folded launches of one eval forward (stem + 16 * 3 + 4 downsample branches)
+struct EvalTapLayout {
+    std::vector<size_t> off;        // byte offset of each unit; off.back() = total bytes
+};
+EvalTapLayout eval_tap_layout(const io_net* net, int N, int H, int W) {
+    EvalTapLayout l;
+    const size_t e = (size_t)io_dtype_bytes(net->dtype);
+    size_t top = 0;
+    auto unit = [&](int h, int w, int ch) {
+        l.off.push_back(top);
+        top += (size_t)N * h * w * ch * e;
+    };
+    unit(H / 2, W / 2, 64);
+    unit(H / 4, W / 4, 64);
+    int h = H / 4, w = W / 4;
+    for (const Block& b : net->blocks) {
+        const int ho = h / b.stride, wo = w / b.stride;
+        unit(h, w, b.planes);
+        unit(ho, wo, b.planes);
+        if (b.down) unit(ho, wo, b.planes * 4);
+        unit(ho, wo, b.planes * 4);
+        h = ho;
+        w = wo;
+    }
+    l.off.push_back(top);
+    return l;
+}
+// what io_net_forward_eval_taps adds to a forward; the product entry points pass none
+struct EvalTaps {
+    char* base = nullptr;           // device buffer of eval_tap_layout(..).off.back() bytes, or nullptr
+    EvalTapLayout layout;
+    size_t next = 0;                // unit the next copy fills
+    int32_t* routes = nullptr;      // host array of kEvalConvs entries, or nullptr
+    int nroutes = 0;
+};
+int eval_tap(const Ctx& c, EvalTaps* tp, const void* src) {
+    if (!tp || !tp->base) return IO_OK;
+    IO_REQUIRE(tp->next + 1 < tp->layout.off.size(), IO_ERR_STATE, "eval taps: more units than the layout has");
+    const size_t o = tp->layout.off[tp->next], bytes = tp->layout.off[tp->next + 1] - o;
+    tp->next += 1;
+    const hipError_t e = hipMemcpyAsync(tp->base + o, src, bytes, hipMemcpyDeviceToDevice, c.st);
+    IO_REQUIRE(e == hipSuccess, IO_ERR_LAUNCH, "eval taps: copy of unit %zu: %s", tp->next - 1, hipGetErrorString(e));
+    return IO_OK;
+}
+
+int run_forward_eval(Ctx& c, const void* x8, float* logits, EvalTaps* tp = nullptr) {
     const io_net* net = c.net;
     const Plan& p = c.plan;
     const int H0 = c.S / 2, H1 = c.S / 4;
+    // conv_folded, then (tapped calls only) which kernel family the launcher sent it to
+    auto folded = [&](const ConvL& L, const BnL& b, const void* x, void* y, int H, int W, const void* add, int relu) -> int {
+        IO_TRY(conv_folded(c, L, b, x, y, H, W, add, relu));
+        if (tp && tp->routes) {
+            IO_REQUIRE(tp->nroutes < kEvalConvs, IO_ERR_STATE, "eval taps: more than %d convolutions", kEvalConvs);
+            tp->routes[tp->nroutes++] = io_debug_last_nt_route();
+        }
+        return (int)IO_OK;
+    };
     {
         FoldTable t;
         t.n = 0;
@@ -591,22 +649,28 @@ int run_forward_eval(Ctx& c, const void* x8, float* logits) {
         IO_TRY(io_check_launch("fold_bn"));
     }
     const int W0 = c.SW / 2;
-    IO_TRY(conv_folded(c, net->stem, net->bn1, x8, c.act(p.a0), c.S, c.SW, nullptr, 1));
+    IO_TRY(folded(net->stem, net->bn1, x8, c.act(p.a0), c.S, c.SW, nullptr, 1));
+    IO_TRY(eval_tap(c, tp, c.act(p.a0)));
     IO_TRY(io_maxpool_fwd_t(c.act(p.a0), c.N, H0, W0, 64, c.act(p.p0), nullptr, c.st, c.dt()));
+    IO_TRY(eval_tap(c, tp, c.act(p.p0)));
     const void* x = c.act(p.p0);
     int H = H1, W = c.SW / 4;
     for (size_t i = 0; i < net->blocks.size(); ++i) {
         const Block& b = net->blocks[i];
         const BlockBufs& bb = p.blk[i];
         const int Ho = H / b.stride, Wo = W / b.stride;
-        IO_TRY(conv_folded(c, b.c1, b.b1, x, c.act(bb.a1), H, W, nullptr, 1));
-        IO_TRY(conv_folded(c, b.c2, b.b2, c.act(bb.a1), c.act(bb.a2), H, W, nullptr, 1));
+        IO_TRY(folded(b.c1, b.b1, x, c.act(bb.a1), H, W, nullptr, 1));
+        IO_TRY(eval_tap(c, tp, c.act(bb.a1)));
+        IO_TRY(folded(b.c2, b.b2, c.act(bb.a1), c.act(bb.a2), H, W, nullptr, 1));
+        IO_TRY(eval_tap(c, tp, c.act(bb.a2)));
         const void* identity = x;
         if (b.down) {
-            IO_TRY(conv_folded(c, b.cd, b.bd, x, c.act(bb.yd), H, W, nullptr, 0));
+            IO_TRY(folded(b.cd, b.bd, x, c.act(bb.yd), H, W, nullptr, 0));
+            IO_TRY(eval_tap(c, tp, c.act(bb.yd)));
             identity = c.act(bb.yd);
         }
-        IO_TRY(conv_folded(c, b.c3, b.b3, c.act(bb.a2), c.act(bb.out), Ho, Wo, identity, 1));
+        IO_TRY(folded(b.c3, b.b3, c.act(bb.a2), c.act(bb.out), Ho, Wo, identity, 1));
+        IO_TRY(eval_tap(c, tp, c.act(bb.out)));
         x = c.act(bb.out);
         H = Ho;
         W = Wo;
@@ -1160,6 +1224,40 @@ extern "C" int io_net_forward_eval_hw(io_net* net, const float* params, float* r
     IO_REQUIRE(ws_bytes >= c.plan.total, IO_ERR_WORKSPACE, "io_net_forward_eval_hw: workspace %zu < %zu bytes", ws_bytes,
                c.plan.total);
     return run_forward_eval(c, x8, logits);
+}
+
+// The same forward with its units copied out (tests/test_gpu_eval_units.py): see include/instaorder_hip.h
+extern "C" size_t io_net_eval_taps_bytes(const io_net* net, int N, int H, int W) {
+    if (check_shape_hw(N, H, W)) return 0;
+    return eval_tap_layout(net, N, H, W).off.back();
+}
+extern "C" long io_net_eval_tap_offset(const io_net* net, int N, int H, int W, int which) {
+    if (check_shape_hw(N, H, W)) return -1;
+    const EvalTapLayout l = eval_tap_layout(net, N, H, W);
+    const int n = (int)l.off.size() - 1;
+    if (which < 0 || which >= n) {
+        io_set_error("io_net_eval_tap_offset: which=%d (0..%d)", which, n - 1);
+        return -1;
+    }
+    return (long)l.off[which];
+}
+extern "C" int io_net_forward_eval_taps(io_net* net, const float* params, float* running, const void* x8, int N, int H,
+                                        int W, void* ws, size_t ws_bytes, float* logits, void* taps, size_t taps_bytes,
+                                        int32_t* routes, int max_routes, hipStream_t st) {
+    IO_TRY(check_shape_hw(N, H, W));
+    Ctx c;
+    IO_TRY(fill_ctx(c, net, params, running, nullptr, N, H, 1, false, ws, st, W));
+    IO_REQUIRE(ws_bytes >= c.plan.total, IO_ERR_WORKSPACE, "io_net_forward_eval_taps: workspace %zu < %zu bytes", ws_bytes,
+               c.plan.total);
+    EvalTaps tp;
+    tp.layout = eval_tap_layout(net, N, H, W);
+    IO_REQUIRE(!taps || taps_bytes >= tp.layout.off.back(), IO_ERR_WORKSPACE,
+               "io_net_forward_eval_taps: tap buffer %zu < %zu bytes", taps_bytes, tp.layout.off.back());
+    IO_REQUIRE(!routes || max_routes >= kEvalConvs, IO_ERR_SHAPE, "io_net_forward_eval_taps: room for %d of %d routes",
+               max_routes, kEvalConvs);
+    tp.base = (char*)taps;
+    tp.routes = routes;
+    return run_forward_eval(c, x8, logits, &tp);
 }
 
 extern "C" int io_net_backward(io_net* net, const float* params, float* grads, const void* x8,

@@ -95,6 +95,34 @@ class Net(object):
                                                    int(W), _ptr(ws), ws.numel() * ws.element_size(), _ptr(logits),
                                                    _stream()), "io_net_forward_eval_hw")
 
+    EVAL_UNITS = 54          # stem, max-pool, per bottleneck a1, a2, (yd), out
+    EVAL_CONVS = 53
+
+    def eval_taps_bytes(self, N, H, W):
+        n = int(self.lib.io_net_eval_taps_bytes(self.handle, int(N), int(H), int(W)))
+        if n == 0:
+            raise RuntimeError("io_net_eval_taps_bytes: " + _lib.last_error())
+        return n
+
+    def eval_tap_offset(self, N, H, W, which):
+        off = int(self.lib.io_net_eval_tap_offset(self.handle, int(N), int(H), int(W), int(which)))
+        if off < 0:
+            raise RuntimeError("io_net_eval_tap_offset: " + _lib.last_error())
+        return off
+
+    def forward_eval_taps(self, params, running, x8, N, H, W, ws, logits, taps=None, routes=False):
+        """forward_eval_hw with every unit copied into ``taps`` (uint8, eval_taps_bytes; layout: eval_tap_offset) --
+        for unit-wise parity checks.  routes=True: returns the kernel family of each of the 53 convolution launches
+        (io_debug_last_nt_route), else None"""
+        _lib.require_gpu()
+        r = (C.c_int32 * self.EVAL_CONVS)(*([-1] * self.EVAL_CONVS)) if routes else None
+        _lib.check(self.lib.io_net_forward_eval_taps(
+            self.handle, _ptr(params), _ptr(running), _ptr(x8), int(N), int(H), int(W), _ptr(ws),
+            ws.numel() * ws.element_size(), _ptr(logits), None if taps is None else _ptr(taps),
+            0 if taps is None else taps.numel() * taps.element_size(), r, self.EVAL_CONVS if routes else 0, _stream()),
+            "io_net_forward_eval_taps")
+        return [int(v) for v in r] if routes else None
+
     def backward(self, params, grads, x8, dlogits, N, S, G, ws, stages=None):
         """stages = (lo, hi): only the backward stages [lo, hi) of io_net_backward_stages (0 = heads + layer4 .. 3 =
         layer1 + stem); None = the whole pass"""

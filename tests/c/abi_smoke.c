@@ -29,6 +29,13 @@ int main(void) {
     ws_train = io_net_workspace_bytes(net, 8, 256, 1);
     printf("tensors %d convs %d bns %d logits %d param_floats %ld running_floats %ld ws_eval %zu ws_train %zu dtype %d\n",
            ntens, convs, bns, io_net_num_logits(net), nparam, nrun, ws_eval, ws_train, io_net_get_dtype(net));
+    /* the tap layout of the eval forward: 54 units packed back to back, 16-byte aligned */
+    if (io_net_eval_tap_offset(net, 2, 32, 256, 0) != 0 || io_net_eval_tap_offset(net, 2, 32, 256, 1) != 2L * 16 * 128 * 64 * 4 ||
+        io_net_eval_tap_offset(net, 2, 32, 256, 53) % 16 != 0 || io_net_eval_tap_offset(net, 2, 32, 256, 54) != -1)
+        return 6;
+    if (io_net_eval_taps_bytes(net, 2, 32, 256) != (size_t)io_net_eval_tap_offset(net, 2, 32, 256, 53) + 2u * 1 * 8 * 2048 * 4 ||
+        io_net_eval_taps_bytes(net, 2, 32, 250) != 0)
+        return 7;
     if (io_net_set_dtype(net, IO_DTYPE_BF16)) return 4;
     printf("bf16 ws_train %zu\n", io_net_workspace_bytes(net, 8, 256, 1));
     /* an invalid request fails with a code and a message, it does not abort */

@@ -288,6 +288,17 @@ def test_rectangular_inference_entries_reject_bad_shapes():
     bad(L().io_net_forward_eval_hw(net.handle, P(params), P(running), P(x8), 2, 96, 64, P(ws), nb // 2, P(logits), ST()))
     assert L().io_net_forward_eval_hw(net.handle, P(params), P(running), P(x8), 2, 96, 64, P(ws), nb, P(logits), ST()) == 0
     torch.cuda.synchronize()
+    # the tapped form of the same forward: a short tap buffer, a short route array
+    tb = net.eval_taps_bytes(2, 96, 64)
+    taps = torch.empty(tb, dtype=torch.uint8, device=DEV)
+    routes = (C.c_int32 * 53)()
+    bad(L().io_net_forward_eval_taps(net.handle, P(params), P(running), P(x8), 2, 96, 64, P(ws), nb, P(logits), P(taps), tb - 1,
+                                     None, 0, ST()))
+    bad(L().io_net_forward_eval_taps(net.handle, P(params), P(running), P(x8), 2, 96, 64, P(ws), nb, P(logits), P(taps), tb,
+                                     routes, 52, ST()))
+    assert L().io_net_forward_eval_taps(net.handle, P(params), P(running), P(x8), 2, 96, 64, P(ws), nb, P(logits), P(taps), tb,
+                                        routes, 53, ST()) == 0
+    torch.cuda.synchronize()
     bad(L().io_pair_planes_u8_hw(P(x8), 16, P(x8), P(x8), 1, 0, 64, None, None, None, P(logits), P(logits), ST()))
     cfg = dict(algo="InstaOrderNet_o", lr=1e-3, weight_decay=1e-4, optim="SGD", backbone_arch="resnet50_cls",
                backbone_param=dict(in_channels=5, num_classes=2), use_rgb=True)
