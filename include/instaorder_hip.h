@@ -450,6 +450,14 @@ int io_mask_pack(const uint8_t* masks, int n, int H, int W, int predicate, int d
  * io_mask_pack of the same H x W.  n_p, n_q <= IO_MASK_MAX_N, H * W < 2^31.  No workspace. */
 int io_mask_pair_counts(const uint32_t* p_bits, int n_p, const uint32_t* q_bits, int n_q, int H, int W, int32_t* counts,
                         hipStream_t stream);
+/* io_mask_bbox_u8: out[i] (int32 [n][5]) = x, y, w, h, count of the pixels of masks[i] (uint8 [n][H][W], mask i at byte
+ * i * H * W, no alignment assumed) that satisfy the predicate (IO_MASK_EQ1 / IO_MASK_NONZERO): the box of
+ * utils.mask_to_bbox -- first column, first row, width, height -- and the number of such pixels; a mask without one gives
+ * 0, 0, 0, 0, 0.  out doubles as the accumulator: the call initialises it, blocks of io_mask_bbox_band_rows() rows add their
+ * extents with integer atomics (any block order gives the same integers) and a finishing kernel writes the five values.
+ * n == 0 returns IO_OK without a launch; n <= IO_MASK_MAX_N, H * W < 2^31.  No workspace. */
+int io_mask_bbox_band_rows(void);
+int io_mask_bbox_u8(const uint8_t* masks, int n, int H, int W, int predicate, int32_t* out, hipStream_t stream);
 /* io_instance_depth_select: per instance i of masks[n][H][W] (uint8) over one disparity map disp[H][W] (fp32), in fp32 as
  * net_forward_midas_pretrained: V_i = 1 / (disp + 1e-6) where masks[i] != 0, k[i] = |V_i|, lo[i] / hi[i] =
  * torch.quantile(V_i, 0.05 / 0.95) (linear rule, exact order statistics), value[i] = clamp(lower median of V_i, lo, hi)

@@ -11,6 +11,7 @@ Public surface mirrors the reference's ``models`` / ``utils`` packages for this 
     from instaorder_amd import rle                 # RLEMasks, RLEReader, decode: run-length (COCO RLE) masks decoded on the device
     from instaorder_amd import poly                # PolyMasks, decode: COCO polygon masks rasterised on the device
     from instaorder_amd import jpeg                # JpegImage, loader, decode: baseline JPEG files decoded on the device
+    from instaorder_amd import readers             # InstaOrderReader, COCOAReader, KINSLVISReader: annotation files -> encoded masks
 
 Importing the package does not load the HIP library; the first op does, and fails loudly when
 it is missing or no gfx950 device is visible (there is no CPU fallback).
@@ -34,7 +35,7 @@ def __getattr__(name):
         ns = _types.SimpleNamespace(resnet50_cls=resnet_cls.resnet50_cls, ResNet=resnet_cls.ResNet,
                                     FixModule=common_utils.FixModule)
         return ns
-    if name in ("rle", "poly", "jpeg"):
+    if name in ("rle", "poly", "jpeg", "readers"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "utils":

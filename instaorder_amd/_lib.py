@@ -281,6 +281,9 @@ SIGNATURES = {
     "io_mask_pack": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     # p_bits, n_p, q_bits, n_q, H, W, counts, stream
     "io_mask_pair_counts": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
+    # masks (uint8), n, H, W, predicate, out (int32 [n][5]), stream
+    "io_mask_bbox_u8": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "io_mask_bbox_band_rows": (_I, []),
     "io_instance_depth_select_workspace_bytes": (_Z, [_I, _I, _I]),
     # disp, H, W, masks, n, method, value, lo, hi, k, workspace, workspace_bytes, stream
     "io_instance_depth_select": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
