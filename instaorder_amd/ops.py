@@ -7,7 +7,10 @@ kernels' [Cout][taps][Cin] (in the activation type) once per call.
 
 There is no CPU path: inputs must live on an MI355X.
 """
+import contextlib
 import ctypes as C
+import os
+from collections import namedtuple
 
 import torch
 
@@ -29,6 +32,16 @@ def _p(t):
 class _WeightDesc(C.Structure):        # io_weight_desc of include/instaorder_hip.h
     _fields_ = [("src", C.c_long), ("dst_op", C.c_long), ("dst_t", C.c_long), ("dst_g", C.c_long), ("Co", C.c_int),
                 ("Ci", C.c_int), ("T", C.c_int), ("Cop", C.c_int), ("Cip", C.c_int)]
+
+
+# A planned filter: stored channel counts, operand [Cop][taps][Cip], its transpose for the data gradient (None for the packed
+# 8-channel stems), the staging view its filter-gradient launch writes.
+PlanEntry = namedtuple("PlanEntry", "Cip Cop op op_t grad")
+# What a conv_bn with ReLU offers the sole consumer of its output (``out._io_offer``), whose data-gradient launch can then run
+# this BatchNorm's backward.  ``link``: the dict both nodes hold -- "_gamma" / "_beta" (the parameters) and, once the consumer
+# has run the backward, "dy" / "dgamma" / "dbeta" (the latter two as autograd gets them); G / M / C: groups, rows, channels of y.
+BnOffer = namedtuple("BnOffer", "link y mean rstd scale shift gamma G M C")
+Folded = namedtuple("Folded", "key wop bias")      # ``w._io_folded``: BatchNorm folded into the filters and a bias (inference)
 
 
 class WeightPlan(object):
@@ -77,6 +90,34 @@ class WeightPlan(object):
         recs, cls._recording = cls._recording, None
         return [r for r in (recs or {}).values() if r[3] == 1]
 
+    @classmethod
+    @contextlib.contextmanager
+    def step(cls, plan, record_for=None, dtype=None, built=None, prepare=True):
+        """The bracket around one training step (forward, backward, gradient gathering): under ``plan`` (or None) and, with
+        ``record_for`` = the flat optimiser, recorded: ``built`` then gets the plan of ``dtype`` operands made from the
+        recording (False: nothing to plan).  prepare=False: the caller runs ``plan.prepare()`` inside the block (a staged
+        capture wants it in its first graph)."""
+        if record_for is not None:
+            cls.start_recording()
+        if plan is not None and prepare:
+            plan.prepare()
+        cls.active = plan
+        try:
+            yield plan
+        finally:
+            cls.active = None
+            if plan is not None:
+                plan.cleared = False
+            recs = cls.stop_recording() if record_for is not None else None
+        if record_for is not None:           # (not after an exception: half a step is no recording)
+            built(cls(record_for, recs, dtype) if recs else False)
+
+    @classmethod
+    def gather_args(cls):
+        """inside the bracket, for optim.gather_grads / gather_stage: what the plan fills, and whether ITS prepare() cleared the buffer"""
+        plan = cls.active
+        return dict(skip=plan.skip if plan is not None else None, prezeroed=plan is not None and plan.cleared)
+
     def __init__(self, optim, recs, dtype):
         spans = {id(p): off for p, (off, k) in zip(optim._params, optim._spans)}
         dev = optim.flat_params.device
@@ -99,13 +140,13 @@ class WeightPlan(object):
         # the flat gradient buffer -- no per-tensor gradient, no copy into the flat buffer (gather_grads made 286 of them
         # per InstaDepthNet_od step: torch._foreach_copy_ decomposes into one hipMemcpyAsync per tensor)
         self.vecs = {}
-        import os
         direct = os.environ.get("IO_DEPTH_DIRECT_GRADS", "1") != "0"      # (0: every BatchNorm gradient through autograd + gather -- A/B runs)
         for q, Cip, _, _ in recs:
             if direct and Cip == -1 and id(q) in spans and q.dim() == 1:
                 off = spans[id(q)]
                 self.vecs[id(q)] = optim.flat_grads[off:off + q.numel()]
         self.skip_ids = None
+        self.cleared = False       # prepare() has cleared optim.flat_grads for the step in flight (reset by the step bracket)
         self.n = len(rows)
         self._row_off = [d.src for _, d in rows]
         self.ops = torch.zeros(max(n_op, 1), device=dev, dtype=dtype)
@@ -114,10 +155,10 @@ class WeightPlan(object):
         self.table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
         for w, d in rows:
             sz = d.Cop * d.T * d.Cip
-            self.entries[id(w)] = (d.Cip, d.Cop,
-                                   self.ops[d.dst_op:d.dst_op + sz].view(d.Cop, d.T, d.Cip),
-                                   self.ops[d.dst_t:d.dst_t + sz].view(d.Cip, d.T, d.Cop) if d.dst_t >= 0 else None,
-                                   self.gk[d.dst_g:d.dst_g + sz].view(d.Cop, d.T, d.Cip))
+            self.entries[id(w)] = PlanEntry(d.Cip, d.Cop,
+                                            self.ops[d.dst_op:d.dst_op + sz].view(d.Cop, d.T, d.Cip),
+                                            self.ops[d.dst_t:d.dst_t + sz].view(d.Cip, d.T, d.Cop) if d.dst_t >= 0 else None,
+                                            self.gk[d.dst_g:d.dst_g + sz].view(d.Cop, d.T, d.Cip))
 
     @property
     def skip(self):
@@ -128,20 +169,24 @@ class WeightPlan(object):
 
     def lookup(self, w, Cip, Cop, dtype):
         e = self.entries.get(id(w))
-        return e if (e is not None and e[0] == Cip and e[1] == Cop and dtype == self.dtype) else None
+        return e if (e is not None and e.Cip == Cip and e.Cop == Cop and dtype == self.dtype) else None
 
     def prepare(self):
+        """-> whether it cleared optim.flat_grads: kept in ``cleared`` until the step's bracket closes (= gather's ``prezeroed``)"""
         if self.n:
             # A planned filter whose gradient kernel does not run in this step (a loss weight switched to 0 after the plan
             # was recorded) must deliver zero, not the previous step's gradient: unpack_grads() copies every entry of gk.
             self.gk.zero_()
-            if self.vecs:
-                # ... and so must a directly written BatchNorm gradient, and every parameter no loss reaches (the occlusion
-                # branch of the reference's InstaDepthNet_od recipe: occ_order_weight 0) -- ONE fill of the flat buffer
-                # instead of one per gradient-less parameter in gather_grads (129 per step)
-                self.optim.flat_grads.zero_()
+        if self.vecs:
+            # ... and so must a directly written BatchNorm gradient, and every parameter no loss reaches (the occlusion
+            # branch of the reference's InstaDepthNet_od recipe: occ_order_weight 0) -- ONE fill of the flat buffer
+            # instead of one per gradient-less parameter in gather_grads (129 per step); whether or not a filter is planned
+            self.optim.flat_grads.zero_()
+            self.cleared = True
+        if self.n:
             _lib.check(_L().io_weights_prepare(_p(self.table), self.n, _p(self.optim.flat_params), _p(self.ops),
                                                1 if self.dtype == torch.bfloat16 else 0, _st()), "io_weights_prepare")
+        return self.cleared
 
     def unpack_grads(self, lo=None, hi=None):
         """after optim.gather_grads(): the planned filters' gradients into their OIHW places in the flat buffer; with
@@ -192,101 +237,215 @@ def nchw_from_nhwc(x):
     return x.permute(0, 3, 1, 2).contiguous()
 
 
+# ---- launch blocks the convolution / BatchNorm nodes are composed of ------------------------------------------------------
+# one convolution as its launches take it; Cs / Co are the STORED channel counts of input and output
+_Geom = namedtuple("_Geom", "N H W Cs Co R S stride pad")
+
+
+def _geom(x, w, stride, pad, Cop):
+    N, H, W_, Cs = x.shape
+    return _Geom(N, H, W_, Cs, Cop, w.shape[2], w.shape[3], stride, pad)
+
+
+def _grouped(g):
+    """the geometry as the grouped launches take it (Cin == Cout: one channel count)"""
+    return g.N, g.H, g.W, g.Co, g.R, g.S, g.stride, g.pad
+
+
+def _conv_out(x, g):
+    Ho, Wo = (g.H + 2 * g.pad - g.R) // g.stride + 1, (g.W + 2 * g.pad - g.S) // g.stride + 1
+    return torch.empty((g.N, Ho, Wo, g.Co), device=x.device, dtype=x.dtype)
+
+
+def _conv_operands(x, w, wsrc, g, dense, planned=True):
+    """OIHW ``wsrc`` (values of the parameter ``w``) -> (operand of the forward, operand the data gradient starts from,
+    PlanEntry or None).  Dense: [Co'][taps][Cs]; planned: the use is noted for a recording, and the operand is the active
+    plan's if that holds the filter in this layout.  Grouped: 64-channel windows and their twin for the data gradient."""
+    Co, Ci, R, S = w.shape
+    if not dense:
+        wc = torch.empty((Co, R * S, 64), device=x.device, dtype=x.dtype)
+        wtc = torch.empty_like(wc)
+        _lib.check(_L().io_gconv_pack(_p(wsrc.contiguous()), Co, Ci, R * S, _p(wc), _p(wtc), _dt(x), _st()), "io_gconv_pack")
+        return wc, wtc, None
+    ent = None
+    if planned:
+        WeightPlan.note(w, g.Cs, g.Co)
+        ent = WeightPlan.active.lookup(w, g.Cs, g.Co, x.dtype) if WeightPlan.active is not None else None
+    if ent is not None:
+        return ent.op, ent.op, ent
+    wk = torch.zeros((g.Co, R * S, g.Cs), device=x.device, dtype=x.dtype)
+    wk[:Co, :, :Ci] = wsrc.permute(0, 2, 3, 1).reshape(Co, R * S, Ci)
+    return wk, wk, None
+
+
+def _conv_fwd(x, wop, y, g, dense):
+    if dense:
+        _lib.check(_L().io_conv2d_fwd_dt(_p(x), _p(wop), _p(y), *g, _dt(x), _dt(x), _st()), "io_conv2d_fwd_dt")
+    else:
+        _lib.check(_L().io_gconv2d_fwd(_p(x), _p(wop), _p(y), *_grouped(g), _dt(x), _st()), "io_gconv2d_fwd")
+
+
+def _conv_dgrad(who, g, x, dy, wback, ent, dense, add=None, prev=None):
+    """-> (data gradient, what is left of ``add``): the dense launch sums ``add`` onto it, the others have no such operand.
+    ``prev``: the BnOffer of x's producer, whose BatchNorm backward then runs in this launch (_fused_dgrad)."""
+    if dense:
+        if g.Cs == 8:
+            raise RuntimeError("ops.%s: no data gradient for the packed 8-channel stem input" % who)
+        wback = ent.op_t if ent is not None else wback.permute(2, 1, 0).contiguous()     # [Cin][taps][Cout]
+    if prev is not None:
+        return _fused_dgrad(g, x, dy, wback, 0 if dense else 64, prev), add
+    dx = torch.empty_like(x)
+    if dense:
+        _lib.check(_L().io_conv2d_dgrad_dt(_p(dy), _p(wback), _p(dx), _p(add), None, *g, _dt(x), _st()), "io_conv2d_dgrad_dt")
+        return dx, None
+    _lib.check(_L().io_gconv2d_dgrad(_p(dy), _p(wback), _p(dx), *_grouped(g), _dt(x), _st()), "io_gconv2d_dgrad")
+    return dx, add
+
+
+def _fused_dgrad(g, x, dy, wt_op, gw, prev):
+    """data gradient + the PRODUCER's BatchNorm backward: ReLU mask recomputed from its y, its two reductions in
+    the epilogue of this launch, then only the apply pass -- the producer node finds its results in the link"""
+    dev = x.device
+    tiles = prev.M // 128
+    nws = 2 * ((tiles + tiles // 64 + prev.G + 2) * prev.C) + 2 * prev.G * prev.C
+    wsf = torch.empty(nws, device=dev, dtype=torch.float32)
+    dz = torch.empty_like(x)
+    dyb = torch.empty_like(x)
+    link = prev.link
+    dg, link["dgamma"] = _grad_dest(link.get("_gamma"), prev.C, dev)
+    db, link["dbeta"] = _grad_dest(link.get("_beta"), prev.C, dev)
+    _lib.check(_L().io_conv2d_dgrad_bnbwd_dt(_p(dy), _p(wt_op), _p(dz), g.N, g.H, g.W, g.Cs, g.Co, g.R, g.S, g.pad,
+                                             _p(prev.y), prev.G, _p(prev.gamma), _p(prev.mean), _p(prev.rstd),
+                                             _p(prev.scale), _p(prev.shift), _p(dg), _p(db), _p(dyb), _p(wsf), nws, _dt(x),
+                                             gw, _st()), "io_conv2d_dgrad_bnbwd_dt")
+    link["dy"] = dyb
+    return dz
+
+
+def _conv_wgrad(g, x, dy, ent, Co, Ci, dense):
+    """-> the filter gradient, OIHW [Co,Ci,R,S]; None for a planned filter (WeightPlan.unpack_grads delivers it)"""
+    L, dev = _L(), x.device
+    if dense:
+        nb = int(L.io_conv2d_wgrad_workspace_bytes(*g))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        dwk = ent.grad if ent is not None else torch.empty((g.Co, g.R * g.S, g.Cs), device=dev, dtype=torch.float32)
+        _lib.check(L.io_conv2d_wgrad_dt(_p(x), _p(dy), _p(dwk), *g, _p(ws), nb, _dt(x), _dt(x), _st()), "io_conv2d_wgrad_dt")
+        return None if ent is not None else dwk[:Co, :, :Ci].reshape(Co, g.R, g.S, Ci).permute(0, 3, 1, 2).contiguous()
+    nb = int(L.io_gconv2d_wgrad_workspace_bytes(*_grouped(g)))
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+    dwc = torch.empty((Co, g.R * g.S, 64), device=dev, dtype=torch.float32)
+    _lib.check(L.io_gconv2d_wgrad(_p(x), _p(dy), _p(dwc), *_grouped(g), _p(ws), nb, _dt(x), _st()), "io_gconv2d_wgrad")
+    dw = torch.empty((Co, Ci, g.R, g.S), device=dev, dtype=torch.float32)
+    _lib.check(L.io_gconv_unpack_grad(_p(dwc), Co, Ci, g.R * g.S, _p(dw), _st()), "io_gconv_unpack_grad")
+    return dw
+
+
+def _momentum(repeat):
+    """R identical module calls advance a running estimate R times with the same statistic:
+    r <- (1-m)^R r + (1 - (1-m)^R) s, i.e. ONE update with momentum 1 - (1-m)^R (m = 0.1)."""
+    return 1.0 - 0.9 ** int(repeat)
+
+
+def _bn_partials(M, Cc, G, dev):
+    npart = int(_L().io_bn_partial_floats(M, Cc, G))
+    return torch.empty(npart, device=dev, dtype=torch.float32), npart
+
+
+def _bn_stats(t, M, Cc, G, gamma, beta, running_mean, running_var, repeat, coeffs):
+    """training: batch statistics of t[M, Cc] in G groups -> ``coeffs``; running estimates advanced in place"""
+    mean, rstd, scale, shift = coeffs
+    part, npart = _bn_partials(M, Cc, G, t.device)
+    _lib.check(_L().io_bn_stats_finalize_dt(_p(t), M, Cc, G, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                                            _momentum(repeat), 1e-5, _p(mean), _p(rstd), _p(scale), _p(shift), _p(part),
+                                            npart, _dt(t), _st()), "io_bn_stats_finalize_dt")
+
+
+def _bn_eval_prepare(Cc, gamma, beta, running_mean, running_var, coeffs):
+    """eval: ``coeffs`` from the running estimates -> rstd"""
+    mean, _, scale, shift = coeffs
+    _lib.check(_L().io_bn_eval_prepare(Cc, _p(gamma), _p(beta), _p(running_mean), _p(running_var), 1e-5, _p(mean),
+                                       _p(scale), _p(shift), _st()), "io_bn_eval_prepare")
+    return scale / gamma
+
+
+def _bn_apply(t, M, Cc, G, batch_stats, mean, scale, shift, identity, relu):
+    out = torch.empty_like(t)
+    _lib.check(_L().io_bn_apply_dt(_p(t), M, Cc, G, 1 if batch_stats else 0, _p(mean), _p(scale), _p(shift), _p(identity),
+                                   None, None, None, int(relu), _p(out), _dt(t), _st()), "io_bn_apply_dt")
+    return out
+
+
+def _grad_dest(q, n, dev):
+    """gradient of the 1-D parameter ``q`` -> (the tensor its kernel writes, what autograd gets for q): the plan's view of the
+    flat buffer and None, or one fresh tensor for both"""
+    t = WeightPlan.grad_target(q)
+    if t is not None:
+        return t, None
+    t = torch.empty(n, device=dev)
+    return t, t
+
+
+def _bn_backward(dout, relu_out, t, M, Cc, G, has_id, gamma, beta, mean, rstd, link=None):
+    """backward of [relu](bn(t) [+ identity]); ``relu_out``: the node's output if it ends in a ReLU
+    -> dt, didentity (None without one), dgamma, dbeta (the latter two as autograd gets them)"""
+    dev = t.device
+    part, npart = _bn_partials(M, Cc, G, dev)
+    coef = torch.empty(2 * G * Cc, device=dev, dtype=torch.float32)
+    if link is not None and "dy" in link:
+        # the sole consumer of the node's output already ran this backward in its data-gradient launch (_fused_dgrad); the
+        # query and the buffers above stay ahead of this test: the step's call sequence and pool layout are what they were
+        return link.pop("dy"), None, link.pop("dgamma"), link.pop("dbeta")
+    dgamma, ret_g = _grad_dest(gamma, Cc, dev)
+    dbeta, ret_b = _grad_dest(beta, Cc, dev)
+    dx = torch.empty_like(t)
+    dz = torch.empty_like(t) if has_id else None          # gradient of the pre-ReLU sum = gradient of `identity`
+    _lib.check(_L().io_bn_bwd_dt(_p(dout), _p(relu_out), None, None, _p(t), M, Cc, G, _p(gamma.detach()), _p(mean),
+                                 _p(rstd), _p(dgamma), _p(dbeta), _p(dx), _p(dz), _p(part), npart, _p(coef), _dt(t), _st()),
+               "io_bn_bwd_dt")
+    return dx, dz, ret_g, ret_b
+
+
 # ---- convolution -------------------------------------------------------------------------------------------------------
 class _Conv(torch.autograd.Function):
     """Dense convolution (models/backbone/resnet_cls.py:23-31, midas/blocks.py:27-38, 133-139).  x[N,H,W,Ci'] where
     Ci' >= Ci is the stored channel count (8 for the 3- / 2-channel stems); w OIHW [Co,Ci,R,S].  Output channels are
     padded to a multiple of 64 when `co_pad` (the 128 -> 32 convolution of output_conv): the extra channels are 0."""
+    dense = True
 
-    @staticmethod
-    def forward(ctx, x, w, stride, pad, co_pad):
+    @classmethod
+    def forward(cls, ctx, x, w, stride, pad, co_pad=False):
         _chk(x, "x")
-        N, H, W_, Cs = x.shape
-        Co, Ci, R, S = w.shape
-        Cop = ((Co + 63) // 64) * 64 if co_pad else Co
-        WeightPlan.note(w, Cs, Cop)
-        ent = WeightPlan.active.lookup(w, Cs, Cop, x.dtype) if WeightPlan.active is not None else None
-        if ent is not None:
-            wk = ent[2]
-        else:
-            wk = torch.zeros((Cop, R * S, Cs), device=x.device, dtype=x.dtype)
-            wk[:Co, :, :Ci] = w.detach().permute(0, 2, 3, 1).reshape(Co, R * S, Ci)
-        Ho, Wo = (H + 2 * pad - R) // stride + 1, (W_ + 2 * pad - S) // stride + 1
-        y = torch.empty((N, Ho, Wo, Cop), device=x.device, dtype=x.dtype)
-        _lib.check(_L().io_conv2d_fwd_dt(_p(x), _p(wk), _p(y), N, H, W_, Cs, Cop, R, S, stride, pad, _dt(x), _dt(x), _st()),
-                   "io_conv2d_fwd_dt")
-        ctx.save_for_backward(x, wk)
-        ctx.ent = ent
-        ctx.geom = (N, H, W_, Cs, Cop, Co, Ci, R, S, stride, pad)
+        Co, Ci = w.shape[:2]
+        if not cls.dense and Co != x.shape[-1]:
+            raise ValueError("grouped conv: Cin must equal Cout")
+        g = _geom(x, w, stride, pad, ((Co + 63) // 64) * 64 if co_pad else Co)
+        wk, wback, ent = _conv_operands(x, w, w.detach(), g, cls.dense)
+        y = _conv_out(x, g)
+        _conv_fwd(x, wk, y, g, cls.dense)
+        ctx.save_for_backward(x, wback)
+        ctx.ent, ctx.geom, ctx.wshape = ent, g, (Co, Ci)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, wk = ctx.saved_tensors
-        N, H, W_, Cs, Cop, Co, Ci, R, S, stride, pad = ctx.geom
+        g, ent = ctx.geom, ctx.ent
         dy = dy.contiguous()
-        L = _L()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if Cs == 8:
-                raise RuntimeError("ops.conv2d: no data gradient for the packed 8-channel stem input")
-            ent = ctx.ent
-            wt = ent[3] if ent is not None else wk.permute(2, 1, 0).contiguous()     # [Cin][taps][Cout]
-            dx = torch.empty_like(x)
-            _lib.check(L.io_conv2d_dgrad_dt(_p(dy), _p(wt), _p(dx), None, None, N, H, W_, Cs, Cop, R, S, stride, pad, _dt(x),
-                                            _st()), "io_conv2d_dgrad_dt")
-        dw = None
-        if ctx.needs_input_grad[1]:
-            ent = ctx.ent
-            nb = int(L.io_conv2d_wgrad_workspace_bytes(N, H, W_, Cs, Cop, R, S, stride, pad))
-            ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=x.device)
-            dwk = ent[4] if ent is not None else torch.empty((Cop, R * S, Cs), device=x.device, dtype=torch.float32)
-            _lib.check(L.io_conv2d_wgrad_dt(_p(x), _p(dy), _p(dwk), N, H, W_, Cs, Cop, R, S, stride, pad, _p(ws), nb, _dt(x),
-                                            _dt(x), _st()), "io_conv2d_wgrad_dt")
-            if ent is None:        # (planned filters: WeightPlan.unpack_grads delivers the gradient)
-                dw = dwk[:Co, :, :Ci].reshape(Co, R, S, Ci).permute(0, 3, 1, 2).contiguous()
+        dx = _conv_dgrad("conv2d", g, x, dy, wk, ent, True)[0] if ctx.needs_input_grad[0] else None
+        dw = _conv_wgrad(g, x, dy, ent, *ctx.wshape, True) if ctx.needs_input_grad[1] else None
         return dx, dw, None, None, None
 
 
-class _GroupedConv(torch.autograd.Function):
+class _GroupedConv(_Conv):
     """Grouped 3x3 convolution of ResNeXt (resnet_cls.py:23-26 with groups=32): w OIHW [C, C/groups, R, S]."""
-
-    @staticmethod
-    def forward(ctx, x, w, stride, pad):
-        _chk(x, "x")
-        N, H, W_, Cc = x.shape
-        Co, cg, R, S = w.shape
-        if Co != Cc:
-            raise ValueError("grouped conv: Cin must equal Cout")
-        L = _L()
-        wc = torch.empty((Cc, R * S, 64), device=x.device, dtype=x.dtype)
-        wtc = torch.empty_like(wc)
-        _lib.check(L.io_gconv_pack(_p(w.detach().contiguous()), Cc, cg, R * S, _p(wc), _p(wtc), _dt(x), _st()),
-                   "io_gconv_pack")
-        Ho, Wo = (H + 2 * pad - R) // stride + 1, (W_ + 2 * pad - S) // stride + 1
-        y = torch.empty((N, Ho, Wo, Cc), device=x.device, dtype=x.dtype)
-        _lib.check(L.io_gconv2d_fwd(_p(x), _p(wc), _p(y), N, H, W_, Cc, R, S, stride, pad, _dt(x), _st()), "io_gconv2d_fwd")
-        ctx.save_for_backward(x, wtc)
-        ctx.geom = (N, H, W_, Cc, cg, R, S, stride, pad)
-        return y
+    dense = False
 
     @staticmethod
     def backward(ctx, dy):
         x, wtc = ctx.saved_tensors
-        N, H, W_, Cc, cg, R, S, stride, pad = ctx.geom
         dy = dy.contiguous()
-        L = _L()
-        dx = torch.empty_like(x)
-        _lib.check(L.io_gconv2d_dgrad(_p(dy), _p(wtc), _p(dx), N, H, W_, Cc, R, S, stride, pad, _dt(x), _st()),
-                   "io_gconv2d_dgrad")
-        nb = int(L.io_gconv2d_wgrad_workspace_bytes(N, H, W_, Cc, R, S, stride, pad))
-        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=x.device)
-        dwc = torch.empty((Cc, R * S, 64), device=x.device, dtype=torch.float32)
-        _lib.check(L.io_gconv2d_wgrad(_p(x), _p(dy), _p(dwc), N, H, W_, Cc, R, S, stride, pad, _p(ws), nb, _dt(x), _st()),
-                   "io_gconv2d_wgrad")
-        dw = torch.empty((Cc, cg, R, S), device=x.device, dtype=torch.float32)
-        _lib.check(L.io_gconv_unpack_grad(_p(dwc), Cc, cg, R * S, _p(dw), _st()), "io_gconv_unpack_grad")
-        return dx, dw, None, None
+        dx, _ = _conv_dgrad("conv2d", ctx.geom, x, dy, wtc, None, False)
+        return dx, _conv_wgrad(ctx.geom, x, dy, None, *ctx.wshape, False), None, None
 
 
 def conv2d(x, w, stride=1, pad=0, groups=1, co_pad=False):
@@ -298,12 +457,6 @@ def conv2d(x, w, stride=1, pad=0, groups=1, co_pad=False):
 
 
 # ---- BatchNorm (+ residual add) (+ ReLU) ---------------------------------------------------------------------------------
-def _momentum(repeat):
-    """R identical module calls advance a running estimate R times with the same statistic:
-    r <- (1-m)^R r + (1 - (1-m)^R) s, i.e. ONE update with momentum 1 - (1-m)^R (m = 0.1)."""
-    return 1.0 - 0.9 ** int(repeat)
-
-
 class _BatchNorm(torch.autograd.Function):
     """nn.BatchNorm2d (+ `out += identity`) (+ nn.ReLU) of resnet_cls.py:96-116.  Training: batch statistics, running
     estimates advanced in place (momentum 0.1, unbiased variance); eval: running estimates.
@@ -317,26 +470,17 @@ class _BatchNorm(torch.autograd.Function):
         _chk(x, "x")
         if training:
             WEIGHTS_EPOCH[0] += 1      # running statistics move (behind torch's version counters): folded operands are stale
-        L = _L()
         Cc = x.shape[-1]
         M = x.numel() // Cc
-        dev = x.device
         G = int(groups) if training else 1
-        mean, rstd, scale, shift = (torch.empty(G * Cc, device=dev, dtype=torch.float32) for _ in range(4))
+        coeffs = mean, rstd, scale, shift = tuple(torch.empty(G * Cc, device=x.device, dtype=torch.float32) for _ in range(4))
+        gd, bd = gamma.detach(), beta.detach()
         if training:
             WeightPlan.note_vec(gamma, beta)
-            npart = int(L.io_bn_partial_floats(M, Cc, G))
-            part = torch.empty(npart, device=dev, dtype=torch.float32)
-            _lib.check(L.io_bn_stats_finalize_dt(_p(x), M, Cc, G, _p(gamma.detach()), _p(beta.detach()), _p(running_mean),
-                                                 _p(running_var), _momentum(repeat), 1e-5, _p(mean), _p(rstd), _p(scale),
-                                                 _p(shift), _p(part), npart, _dt(x), _st()), "io_bn_stats_finalize_dt")
+            _bn_stats(x, M, Cc, G, gd, bd, running_mean, running_var, repeat, coeffs)
         else:
-            _lib.check(L.io_bn_eval_prepare(Cc, _p(gamma.detach()), _p(beta.detach()), _p(running_mean), _p(running_var),
-                                            1e-5, _p(mean), _p(scale), _p(shift), _st()), "io_bn_eval_prepare")
-            rstd = scale / gamma.detach()
-        out = torch.empty_like(x)
-        _lib.check(L.io_bn_apply_dt(_p(x), M, Cc, G, 1 if training else 0, _p(mean), _p(scale), _p(shift), _p(identity), None,
-                                    None, None, int(relu), _p(out), _dt(x), _st()), "io_bn_apply_dt")
+            rstd = _bn_eval_prepare(Cc, gd, bd, running_mean, running_var, coeffs)
+        out = _bn_apply(x, M, Cc, G, training, mean, scale, shift, identity, relu)
         ctx.save_for_backward(x, out, gamma, mean, rstd)
         ctx.beta = beta
         ctx.cfg = (M, Cc, bool(relu), identity is not None, bool(training), G)
@@ -348,21 +492,9 @@ class _BatchNorm(torch.autograd.Function):
         M, Cc, relu, has_id, training, G = ctx.cfg
         if not training:
             raise RuntimeError("ops.batch_norm: backward through eval-mode BatchNorm is not implemented")
-        L = _L()
-        dout = dout.contiguous()
-        dev = x.device
-        npart = int(L.io_bn_partial_floats(M, Cc, G))
-        part = torch.empty(npart, device=dev, dtype=torch.float32)
-        coef = torch.empty(2 * G * Cc, device=dev, dtype=torch.float32)
-        tg, tb = WeightPlan.grad_target(gamma), WeightPlan.grad_target(ctx.beta)
-        dgamma = tg if tg is not None else torch.empty(Cc, device=dev)
-        dbeta = tb if tb is not None else torch.empty(Cc, device=dev)
-        dx = torch.empty_like(x)
-        dz = torch.empty_like(x) if has_id else None          # gradient of the pre-ReLU sum = gradient of `identity`
-        _lib.check(L.io_bn_bwd_dt(_p(dout), _p(out) if relu else None, None, None, _p(x), M, Cc, G, _p(gamma.detach()),
-                                  _p(mean), _p(rstd), _p(dgamma), _p(dbeta), _p(dx), _p(dz), _p(part), npart, _p(coef),
-                                  _dt(x), _st()), "io_bn_bwd_dt")
-        return dx, (None if tg is not None else dgamma), (None if tb is not None else dbeta), None, None, None, None, dz, None, None
+        dx, dz, dgamma, dbeta = _bn_backward(dout.contiguous(), out if relu else None, x, M, Cc, G, has_id, gamma, ctx.beta,
+                                             mean, rstd)
+        return dx, dgamma, dbeta, None, None, None, None, dz, None, None
 
 
 def batch_norm(x, gamma, beta, running_mean, running_var, training, relu=False, identity=None, groups=1, repeat=1):
@@ -371,224 +503,109 @@ def batch_norm(x, gamma, beta, running_mean, running_var, training, relu=False, 
     return _BatchNorm.apply(x, gamma, beta, running_mean, running_var, training, relu, identity, groups, repeat)
 
 
+def _conv_bn_infer(x, w, gamma, beta, running_mean, running_var, stride, pad, groups, relu, identity):
+    """inference: the BatchNorm is folded into the filters (scaled per output channel) and a bias; the convolution's
+    epilogue adds bias (+ identity) (+ ReLU) -- no pass over the conv output.  The folded operands are kept on the
+    parameter until the weights change (torch version counters + WEIGHTS_EPOCH, which the HIP-side optimiser bumps): an
+    inference loop re-packs nothing."""
+    dense = groups == 1
+    g = _geom(x, w, stride, pad, w.shape[0])
+    key = (x.dtype, g.Cs, WEIGHTS_EPOCH[0], w._version, gamma._version, beta._version, running_mean._version,
+           running_var._version)
+    hit = getattr(w, "_io_folded", None)
+    if hit is None or hit.key != key:
+        fscale = gamma.detach() / torch.sqrt(running_var + 1e-5)
+        fbias = (beta.detach() - running_mean * fscale).contiguous()
+        wsrc = w.detach() * fscale.view(-1, 1, 1, 1)
+        hit = w._io_folded = Folded(key, _conv_operands(x, w, wsrc, g, dense, planned=False)[0], fbias)
+    y = _conv_out(x, g)
+    _lib.check(_L().io_conv2d_fwd_bias_dt(_p(x), _p(hit.wop), _p(y), *g, _p(hit.bias), _p(identity), int(relu), _dt(x),
+                                          0 if dense else 64, _st()), "io_conv2d_fwd_bias_dt")
+    return y
+
+
+def _conv_bn_train(ctx, x, w, gamma, beta, running_mean, running_var, stride, pad, groups, relu, identity, bn_groups,
+                   repeat, prev):
+    """training: batch statistics in the convolution's epilogue where the rows per statistics group are whole 128-row
+    tiles, else convolution + statistics pass; then the apply pass.  Fills ``ctx`` for _ConvBn.backward."""
+    WEIGHTS_EPOCH[0] += 1      # running statistics move (behind torch's version counters): folded operands are stale
+    L = _L()
+    Co, Cig = w.shape[:2]
+    dense = groups == 1
+    g = _geom(x, w, stride, pad, Co)
+    wop, wback, ent = _conv_operands(x, w, w.detach(), g, dense)
+    y = _conv_out(x, g)
+    M, G = y.numel() // Co, int(bn_groups)
+    coeffs = mean, rstd, scale, shift = tuple(torch.empty(G * Co, device=x.device, dtype=torch.float32) for _ in range(4))
+    gd, bd = gamma.detach(), beta.detach()
+    WeightPlan.note_vec(gamma, beta)
+    tiled = M % G == 0 and (M // G) % 128 == 0
+    if tiled:
+        nws = int(L.io_conv2d_bnstats_workspace_floats(g.N, g.H, g.W, Co, g.R, g.S, stride, pad, G))
+        ws = torch.empty(nws, device=x.device, dtype=torch.float32)
+        _lib.check(L.io_conv2d_fwd_bnstats_dt(_p(x), _p(wop), _p(y), *g, G, _p(gd), _p(bd), _p(running_mean),
+                                              _p(running_var), _momentum(repeat), 1e-5, _p(mean), _p(rstd), _p(scale),
+                                              _p(shift), _p(ws), nws, _dt(x), 0 if dense else 64, _st()),
+                   "io_conv2d_fwd_bnstats_dt")
+    else:
+        _conv_fwd(x, wop, y, g, dense)
+        _bn_stats(y, M, Co, G, gd, bd, running_mean, running_var, repeat, coeffs)
+    out = _bn_apply(y, M, Co, G, True, mean, scale, shift, identity, relu)
+    ctx.save_for_backward(x, wback, y, out, gamma, mean, rstd)
+    ctx.beta, ctx.ent, ctx.geom = beta, ent, g
+    ctx.cfg = (Cig, dense, M, G, bool(relu), identity is not None)
+    # Cross-node fusion of the BatchNorm backward (see conv_bn's `sole`): as PRODUCER of relu(bn(y)) this node offers
+    # what a consumer's data-gradient epilogue needs; as CONSUMER of such a tensor it keeps the producer's offer.
+    if relu and identity is None and tiled and Co % 64 == 0:
+        ctx.link = {"_gamma": gamma, "_beta": beta}
+        _ConvBn.last_offer = BnOffer(ctx.link, y, mean, rstd, scale, shift, gd, G, M, Co)
+    if prev is not None and stride == 1 and prev.M == g.N * g.H * g.W and prev.C == g.Cs and (dense or Co == g.Cs):
+        ctx.prev = prev
+    return out
+
+
 class _ConvBn(torch.autograd.Function):
     """conv (dense or grouped) -> BatchNorm (+ identity) (+ ReLU) as ONE node: in training mode the batch statistics are
     accumulated in the convolution's epilogue (per 128-row tile, merged with Chan's update) whenever the rows per
     statistics group are a multiple of 128 -- no separate pass over the conv output (resnet_cls.py:99-114)."""
+    last_offer = None      # the BnOffer of the forward that just ran, handed over to conv_bn (which hangs it on the output)
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, running_mean, running_var, stride, pad, groups, training, relu, identity,
                 bn_groups, repeat, prev, fork):
         _chk(x, "x")
-        ctx.prev = None
-        ctx.link = None
-        ctx.fork = bool(fork)
-        out = _ConvBn._forward(ctx, x, w, gamma, beta, running_mean, running_var, stride, pad, groups, training, relu,
-                               identity, bn_groups, repeat, prev)
+        if groups != 1 and (w.shape[0] != x.shape[-1] or w.shape[0] // groups != w.shape[1]):
+            raise ValueError("grouped conv: expected [C, C/groups, R, S] filters on C input channels")
+        ctx.prev = ctx.link = _ConvBn.last_offer = None
+        ctx.training = bool(training)
+        if training:
+            out = _conv_bn_train(ctx, x, w, gamma, beta, running_mean, running_var, stride, pad, groups, relu, identity,
+                                 bn_groups, repeat, prev)
+        else:
+            out = _conv_bn_infer(x, w, gamma, beta, running_mean, running_var, stride, pad, groups, relu, identity)
         # fork: x comes back as a second output (an alias) -- for the residual connection of the Bottleneck this convolution
         # opens -- so that the gradient of that path arrives HERE and rides in the `add` operand of the data-gradient
         # launch instead of being summed onto dx by a separate ATen kernel of the autograd engine
         return (out, x) if fork else out
 
     @staticmethod
-    def _forward(ctx, x, w, gamma, beta, running_mean, running_var, stride, pad, groups, training, relu, identity,
-                 bn_groups, repeat, prev):
-        _ConvBn.last_offer = None
-        if training:
-            WEIGHTS_EPOCH[0] += 1      # running statistics move (behind torch's version counters): folded operands are stale
-        L = _L()
-        dev, dt = x.device, _dt(x)
-        N, H, W_, Cs = x.shape
-        Co, Cig, R, S = w.shape
-        dense = groups == 1
-        wsrc = w.detach()
-        cache_key = None
-        if not training:
-            # inference: the BatchNorm is folded into the filters (scaled per output channel) and a bias; the
-            # convolution's epilogue adds bias (+ identity) (+ ReLU) -- no pass over the conv output.  The folded
-            # operands are kept on the parameter until the weights change (torch version counters + WEIGHTS_EPOCH,
-            # which the HIP-side optimiser bumps): an inference loop re-packs nothing.
-            cache_key = (x.dtype, Cs, WEIGHTS_EPOCH[0], w._version, gamma._version, beta._version, running_mean._version,
-                         running_var._version)
-            hit = getattr(w, "_io_folded", None)
-            if hit is not None and hit[0] == cache_key:
-                wop, fbias = hit[1], hit[2]
-                Ho, Wo = (H + 2 * pad - R) // stride + 1, (W_ + 2 * pad - S) // stride + 1
-                y = torch.empty((N, Ho, Wo, Co), device=dev, dtype=x.dtype)
-                _lib.check(L.io_conv2d_fwd_bias_dt(_p(x), _p(wop), _p(y), N, H, W_, Cs, Co, R, S, stride, pad, _p(fbias),
-                                                   _p(identity), int(relu), dt, 0 if dense else 64, _st()),
-                           "io_conv2d_fwd_bias_dt")
-                ctx.cfg = (N, H, W_, Cs, Co, Cig, R, S, stride, pad, dense, N * Ho * Wo, 1, bool(relu),
-                           identity is not None, False)
-                return y
-            fscale = gamma.detach() / torch.sqrt(running_var + 1e-5)
-            fbias = (beta.detach() - running_mean * fscale).contiguous()
-            wsrc = wsrc * fscale.view(-1, 1, 1, 1)
-        ent = None
-        if dense:
-            if training:
-                WeightPlan.note(w, Cs, Co)
-                ent = WeightPlan.active.lookup(w, Cs, Co, x.dtype) if WeightPlan.active is not None else None
-            if ent is not None:
-                wop = ent[2]
-            else:
-                wop = torch.zeros((Co, R * S, Cs), device=dev, dtype=x.dtype)
-                wop[:, :, :Cig] = wsrc.permute(0, 2, 3, 1).reshape(Co, R * S, Cig)
-            wback = wop
-        else:
-            if Co != Cs or Co // groups != Cig:
-                raise ValueError("grouped conv: expected [C, C/groups, R, S] filters on C input channels")
-            wop = torch.empty((Co, R * S, 64), device=dev, dtype=x.dtype)
-            wback = torch.empty_like(wop)
-            _lib.check(L.io_gconv_pack(_p(wsrc.contiguous()), Co, Cig, R * S, _p(wop), _p(wback), dt, _st()),
-                       "io_gconv_pack")
-        Ho, Wo = (H + 2 * pad - R) // stride + 1, (W_ + 2 * pad - S) // stride + 1
-        M = N * Ho * Wo
-        G = int(bn_groups) if training else 1
-        y = torch.empty((N, Ho, Wo, Co), device=dev, dtype=x.dtype)
-        if not training:
-            w._io_folded = (cache_key, wop, fbias)
-            _lib.check(L.io_conv2d_fwd_bias_dt(_p(x), _p(wop), _p(y), N, H, W_, Cs, Co, R, S, stride, pad, _p(fbias),
-                                               _p(identity), int(relu), dt, 0 if dense else 64, _st()),
-                       "io_conv2d_fwd_bias_dt")
-            ctx.cfg = (N, H, W_, Cs, Co, Cig, R, S, stride, pad, dense, M, G, bool(relu), identity is not None, False)
-            return y
-        mean, rstd, scale, shift = (torch.empty(G * Co, device=dev, dtype=torch.float32) for _ in range(4))
-        gd, bd = gamma.detach(), beta.detach()
-        if training:
-            WeightPlan.note_vec(gamma, beta)
-        ctx.beta = beta
-        if training and M % G == 0 and (M // G) % 128 == 0:
-            nws = int(L.io_conv2d_bnstats_workspace_floats(N, H, W_, Co, R, S, stride, pad, G))
-            ws = torch.empty(nws, device=dev, dtype=torch.float32)
-            _lib.check(L.io_conv2d_fwd_bnstats_dt(_p(x), _p(wop), _p(y), N, H, W_, Cs, Co, R, S, stride, pad, G, _p(gd), _p(bd),
-                                                  _p(running_mean), _p(running_var), _momentum(repeat), 1e-5, _p(mean),
-                                                  _p(rstd), _p(scale), _p(shift), _p(ws), nws, dt, 0 if dense else 64, _st()),
-                       "io_conv2d_fwd_bnstats_dt")
-        else:
-            if dense:
-                _lib.check(L.io_conv2d_fwd_dt(_p(x), _p(wop), _p(y), N, H, W_, Cs, Co, R, S, stride, pad, dt, dt, _st()),
-                           "io_conv2d_fwd_dt")
-            else:
-                _lib.check(L.io_gconv2d_fwd(_p(x), _p(wop), _p(y), N, H, W_, Co, R, S, stride, pad, dt, _st()), "io_gconv2d_fwd")
-            if training:
-                npart = int(L.io_bn_partial_floats(M, Co, G))
-                part = torch.empty(npart, device=dev, dtype=torch.float32)
-                _lib.check(L.io_bn_stats_finalize_dt(_p(y), M, Co, G, _p(gd), _p(bd), _p(running_mean), _p(running_var),
-                                                     _momentum(repeat), 1e-5, _p(mean), _p(rstd), _p(scale), _p(shift),
-                                                     _p(part), npart, dt, _st()), "io_bn_stats_finalize_dt")
-            else:
-                _lib.check(L.io_bn_eval_prepare(Co, _p(gd), _p(bd), _p(running_mean), _p(running_var), 1e-5, _p(mean),
-                                                _p(scale), _p(shift), _st()), "io_bn_eval_prepare")
-                rstd = scale / gd
-        out = torch.empty_like(y)
-        _lib.check(L.io_bn_apply_dt(_p(y), M, Co, G, 1 if training else 0, _p(mean), _p(scale), _p(shift), _p(identity), None,
-                                    None, None, int(relu), _p(out), dt, _st()), "io_bn_apply_dt")
-        ctx.save_for_backward(x, wback, y, out, gamma, mean, rstd)
-        ctx.ent = ent
-        ctx.cfg = (N, H, W_, Cs, Co, Cig, R, S, stride, pad, dense, M, G, bool(relu), identity is not None, bool(training))
-        # Cross-node fusion of the BatchNorm backward (see conv_bn's `sole`): as PRODUCER of relu(bn(y)) this node offers
-        # what a consumer's data-gradient epilogue needs; as CONSUMER of such a tensor it keeps the producer's offer.
-        if training and relu and identity is None and M % G == 0 and (M // G) % 128 == 0 and Co % 64 == 0:
-            ctx.link = {"_gamma": gamma, "_beta": beta}       # (the parameters: a consumer that runs this BatchNorm's backward asks WeightPlan where their gradients go)
-            _ConvBn.last_offer = (ctx.link, y, mean, rstd, scale, shift, gamma.detach(), G, M, Co)
-        else:
-            _ConvBn.last_offer = None
-        if prev is not None and stride == 1 and prev[8] == N * H * W_ and prev[9] == Cs and (dense or Co == Cs):
-            ctx.prev = prev
-        return out
-
-    @staticmethod
     def backward(ctx, dout, dfork=None):
-        N, H, W_, Cs, Co, Cig, R, S, stride, pad, dense, M, G, relu, has_id, training = ctx.cfg
-        if not training:
+        if not ctx.training:
             raise RuntimeError("ops.conv_bn: backward through eval-mode BatchNorm is not implemented")
+        Cig, dense, M, G, relu, has_id = ctx.cfg
+        g, ent, prev, link = ctx.geom, ctx.ent, ctx.prev, ctx.link
         if dfork is not None:
             dfork = dfork.contiguous()
         x, wback, y, out, gamma, mean, rstd = ctx.saved_tensors
-        L = _L()
-        dev, dt = x.device, _dt(x)
-        dout = dout.contiguous()
-        npart = int(L.io_bn_partial_floats(M, Co, G))
-        part = torch.empty(npart, device=dev, dtype=torch.float32)
-        coef = torch.empty(2 * G * Co, device=dev, dtype=torch.float32)
-        tg, tb = WeightPlan.grad_target(gamma), WeightPlan.grad_target(ctx.beta)
-        link = ctx.link
-        if link is not None and "dy" in link:
-            # the sole consumer of this node's output already ran this BatchNorm's backward in its data-gradient launch
-            # (and wrote dgamma / dbeta to the same targets)
-            dy, dgamma, dbeta = link.pop("dy"), link.pop("dgamma"), link.pop("dbeta")
-            dz = None
-        else:
-            dgamma = tg if tg is not None else torch.empty(Co, device=dev)
-            dbeta = tb if tb is not None else torch.empty(Co, device=dev)
-            dy = torch.empty_like(y)
-            dz = torch.empty_like(y) if has_id else None
-            _lib.check(L.io_bn_bwd_dt(_p(dout), _p(out) if relu else None, None, None, _p(y), M, Co, G, _p(gamma.detach()),
-                                      _p(mean), _p(rstd), _p(dgamma), _p(dbeta), _p(dy), _p(dz), _p(part), npart, _p(coef),
-                                      dt, _st()), "io_bn_bwd_dt")
+        dy, dz, dgamma, dbeta = _bn_backward(dout.contiguous(), out if relu else None, y, M, g.Co, G, has_id, gamma, ctx.beta,
+                                             mean, rstd, link)
         dx = None
-        ent = getattr(ctx, "ent", None)
-        prev = ctx.prev
-
-        def fused_dgrad(wt_op, gw):
-            """data gradient + the PRODUCER's BatchNorm backward: ReLU mask recomputed from its y, its two reductions in
-            the epilogue of this launch, then only the apply pass -- the producer node finds its results in the link"""
-            link, yp, mean_p, rstd_p, scale_p, shift_p, gamma_p, Gp, Mp, Cp = prev
-            tiles = Mp // 128
-            nws = 2 * ((tiles + tiles // 64 + Gp + 2) * Cp) + 2 * Gp * Cp
-            wsf = torch.empty(nws, device=dev, dtype=torch.float32)
-            dz = torch.empty_like(x)
-            dyb = torch.empty_like(x)
-            tgp, tbp = WeightPlan.grad_target(link.get("_gamma")), WeightPlan.grad_target(link.get("_beta"))
-            dg = tgp if tgp is not None else torch.empty(Cp, device=dev)
-            db = tbp if tbp is not None else torch.empty(Cp, device=dev)
-            _lib.check(L.io_conv2d_dgrad_bnbwd_dt(_p(dy), _p(wt_op), _p(dz), N, H, W_, Cs, Co, R, S, pad, _p(yp), Gp,
-                                                  _p(gamma_p), _p(mean_p), _p(rstd_p), _p(scale_p), _p(shift_p), _p(dg),
-                                                  _p(db), _p(dyb), _p(wsf), nws, dt, gw, _st()), "io_conv2d_dgrad_bnbwd_dt")
-            link["dy"], link["dgamma"], link["dbeta"] = dyb, dg, db
-            return dz
-
-        if dense:
-            if ctx.needs_input_grad[0]:
-                if Cs == 8:
-                    raise RuntimeError("ops.conv_bn: no data gradient for the packed 8-channel stem input")
-                wt = ent[3] if ent is not None else wback.permute(2, 1, 0).contiguous()
-                if prev is not None:
-                    dx = fused_dgrad(wt, 0)
-                else:
-                    dx = torch.empty_like(x)
-                    _lib.check(L.io_conv2d_dgrad_dt(_p(dy), _p(wt), _p(dx), _p(dfork), None, N, H, W_, Cs, Co, R, S, stride, pad,
-                                                    dt, _st()), "io_conv2d_dgrad_dt")
-                    dfork = None                 # (summed inside the launch)
-            nb = int(L.io_conv2d_wgrad_workspace_bytes(N, H, W_, Cs, Co, R, S, stride, pad))
-            ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
-            dwk = ent[4] if ent is not None else torch.empty((Co, R * S, Cs), device=dev, dtype=torch.float32)
-            _lib.check(L.io_conv2d_wgrad_dt(_p(x), _p(dy), _p(dwk), N, H, W_, Cs, Co, R, S, stride, pad, _p(ws), nb, dt, dt,
-                                            _st()), "io_conv2d_wgrad_dt")
-            # (planned filters: WeightPlan.unpack_grads delivers the gradient)
-            dw = None if ent is not None else dwk[:, :, :Cig].reshape(Co, R, S, Cig).permute(0, 3, 1, 2).contiguous()
-        else:
-            if prev is not None:
-                dx = fused_dgrad(wback, 64)
-            else:
-                dx = torch.empty_like(x)
-                _lib.check(L.io_gconv2d_dgrad(_p(dy), _p(wback), _p(dx), N, H, W_, Co, R, S, stride, pad, dt, _st()),
-                           "io_gconv2d_dgrad")
-            nb = int(L.io_gconv2d_wgrad_workspace_bytes(N, H, W_, Co, R, S, stride, pad))
-            ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
-            dwc = torch.empty((Co, R * S, 64), device=dev, dtype=torch.float32)
-            _lib.check(L.io_gconv2d_wgrad(_p(x), _p(dy), _p(dwc), N, H, W_, Co, R, S, stride, pad, _p(ws), nb, dt, _st()),
-                       "io_gconv2d_wgrad")
-            dw = torch.empty((Co, Cig, R, S), device=dev, dtype=torch.float32)
-            _lib.check(L.io_gconv_unpack_grad(_p(dwc), Co, Cig, R * S, _p(dw), _st()), "io_gconv_unpack_grad")
+        if ctx.needs_input_grad[0] or not dense:
+            dx, dfork = _conv_dgrad("conv_bn", g, x, dy, wback, ent, dense, dfork, prev)
+        dw = _conv_wgrad(g, x, dy, ent, g.Co, Cig, dense)
         if dfork is not None:                    # (forms whose data gradient has no add operand: summed here)
             dx = dfork if dx is None else dx + dfork
-        return (dx, dw, (None if tg is not None else dgamma), (None if tb is not None else dbeta), None, None, None, None, None,
-                None, None, dz, None, None, None, None)
-
-
-_ConvBn.last_offer = None
+        return (dx, dw, dgamma, dbeta, None, None, None, None, None, None, None, dz, None, None, None, None)
 
 
 def conv_bn(x, w, gamma, beta, running_mean, running_var, stride, pad, groups, training, relu=False, identity=None,
@@ -604,7 +621,7 @@ def conv_bn(x, w, gamma, beta, running_mean, running_var, stride, pad, groups, t
     if repeat > 1 and bn_groups > 1:
         raise ValueError("conv_bn: repeat and bn_groups are exclusive")
     prev = getattr(x, "_io_offer", None) if (sole and training) else None
-    if prev is not None and prev[7] != (int(bn_groups) if training else 1):
+    if prev is not None and prev.G != int(bn_groups):
         prev = None
     fork = bool(fork and training and torch.is_grad_enabled() and x.requires_grad)
     out = _ConvBn.apply(x, w, gamma, beta, running_mean, running_var, stride, pad, groups, training, relu, identity,
@@ -769,7 +786,7 @@ def add(a, b):
     return _Add.apply(a, b)
 
 
-class _AddShared(torch.autograd.Function):
+class _AddShared(_Add):
     """a + b where b is a tensor OTHER STREAMS consume too (the encoder features injected into an order branch that runs on a
     side stream, midas/midas_net.py:190-197).  The backward hands b its OWN copy of the gradient.  With `return dy, dy`
     (what _Add does, and torch's own AddBackward) the branch's next backward node and the node behind b -- on the main
@@ -778,14 +795,6 @@ class _AddShared(torch.autograd.Function):
     kernels of the branch that are still queued on the side stream hold no reference: they then read a gradient that
     already contains the other branch's.  Found in round 5 (two processes sharing a GPU: one branch's layers below the
     injection point and the encoder stage under it got gradients 10 % off, run to run; tools/depth_eager_race.py)."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        _chk(a, "a")
-        _chk(b, "b")
-        out = torch.empty_like(a)
-        _lib.check(_L().io_add(_p(a), _p(b), a.numel(), _p(out), _dt(a), _st()), "io_add")
-        return out
 
     @staticmethod
     def backward(ctx, dy):

@@ -26,6 +26,25 @@ def _dev(t, dtype=None):
     return t.to(dtype) if dtype is not None and t.dtype != dtype else t
 
 
+def _detached(logs, loss):
+    return ({k: (v.detach() if torch.is_tensor(v) else v) for k, v in logs.items()},
+            loss.detach() if torch.is_tensor(loss) else loss)
+
+
+def _cloned(logs, loss):
+    """a replayed graph writes the same output tensors every time: callers get copies"""
+    return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in logs.items()}, loss.clone()
+
+
+def _backward_roots(heads, loss_smooth):
+    """(roots, their gradients) for the backward pass: the order heads with the gradients io_order_loss computed, and the
+    smoothness loss where it takes part"""
+    roots, grads = [h for h, _ in heads], [g for _, g in heads]
+    if torch.is_tensor(loss_smooth) and loss_smooth.requires_grad:
+        roots.append(loss_smooth)
+        grads.append(torch.ones_like(loss_smooth))
+    return roots, grads
+
 
 def _force_overlap_requested():
     """IO_COMM_OVERLAP=force: the staged data-parallel step on ONE rank.  It issues the backend's all-reduce between the
@@ -504,39 +523,32 @@ class _DepthBase(SingleStageModel):
             logs, loss, _, _ = self._losses(outs, False)
         return logs, {"loss": loss}
 
+    def _live_plan(self):
+        """-> (the ops.WeightPlan this step runs with, or None; whether this step records one)"""
+        plan = self._wplan if (self._wplan and self.PAIR_MODE and self._wplan.dtype == self.net._act_dtype()) else None
+        return plan, self._wplan is None and self.PAIR_MODE and hasattr(self.optim, "_spans")
+
+    def _plan_step(self, prepare=True):
+        """the bracket (ops.WeightPlan.step) for one training step, with the live plan; a plan recorded in it becomes ``_wplan``"""
+        from .ops import WeightPlan
+        plan, recording = self._live_plan()
+        return WeightPlan.step(plan, self.optim if recording else None, self.net._act_dtype(),
+                               lambda built: setattr(self, "_wplan", built), prepare)
+
     def _fwd_loss_bwd(self):
         """forward (both mask orders) + the five loss terms + backward + gradients gathered into the flat buffer"""
-        from . import ops
-        flat = hasattr(self.optim, "gather_grads")          # FlatSGD / FlatAdam; a torch optimiser keeps per-tensor gradients
-        plan = self._wplan if (self._wplan and self.PAIR_MODE and self._wplan.dtype == self.net._act_dtype()) else None
-        recording = self._wplan is None and self.PAIR_MODE and hasattr(self.optim, "_spans")
-        if recording:
-            ops.WeightPlan.start_recording()
-        if plan is not None:
-            plan.prepare()                       # every dense filter of the net, one launch
-        ops.WeightPlan.active = plan
-        try:
+        from .ops import WeightPlan
+        with self._plan_step() as plan:          # (prepare: every dense filter of the net, one launch)
             outs = self._run(True)
             logs, loss, heads, loss_smooth = self._losses(outs, True)
             self.optim.zero_grad()
-            roots, grads = [h for h, _ in heads], [g for _, g in heads]
-            if torch.is_tensor(loss_smooth) and loss_smooth.requires_grad:
-                roots.append(loss_smooth)
-                grads.append(torch.ones_like(loss_smooth))
-            torch.autograd.backward(roots, grads)
+            torch.autograd.backward(*_backward_roots(heads, loss_smooth))
             self.net.join_side_streams()
-        finally:
-            ops.WeightPlan.active = None
-            recs = ops.WeightPlan.stop_recording() if recording else None
-        if flat:
-            self.optim.gather_grads(skip=plan.skip if plan is not None else None,
-                                    prezeroed=bool(plan is not None and plan.vecs))
-        if plan is not None:
-            plan.unpack_grads()                  # ... and their gradients back, one launch
-        if recording:
-            self._wplan = ops.WeightPlan(self.optim, recs, self.net._act_dtype()) if recs else False
-        logs = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in logs.items()}
-        return logs, (loss.detach() if torch.is_tensor(loss) else loss)
+            if hasattr(self.optim, "gather_grads"):          # FlatSGD / FlatAdam; a torch optimiser keeps per-tensor gradients
+                self.optim.gather_grads(**WeightPlan.gather_args())
+            if plan is not None:
+                plan.unpack_grads()              # ... and their gradients back, one launch
+        return _detached(logs, loss)
 
     # ---- data-parallel step: staged backward + bucketed gradient exchange ----------------------------------------------
     STAGE_NAMES = ("heads+order branches+decoder", "encoder layer4", "encoder layer3", "encoder layer2+layer1")
@@ -579,34 +591,31 @@ class _DepthBase(SingleStageModel):
     def _staged_steps(self, plan):
         """Generator: forward (both mask orders) + the loss terms, then the backward pass stage by stage; yields the stage
         index each time that stage's slice of the flat gradient buffer is final (gathered, planned filters unpacked).
-        The cut points are the encoder's stage outputs l1..l4 (midas_net._encode_decode): torch.autograd.grad from the
+        Runs inside the bracket of ``plan`` (_plan_step).  The cut points are the encoder's stage outputs l1..l4
+        (midas_net._encode_decode): torch.autograd.grad from the
         losses to (parameters behind the encoder, l1..l4), then layer4 from dl4 to (its parameters, l3), and so on -- the
         gradients a boundary collects from several consumers are summed exactly as one backward() call would.  The
         result lands in ``self._staged_out``."""
         opt = self.optim
         stages = self._stage_plan()
         P = [[opt._params[i] for i in idx] for _, idx in stages]
-        skip = plan.skip if plan is not None else None
+        from .ops import WeightPlan
         self.net._stage_cut = True            # every consumer of an encoder stage output reads a detached alias of it
         try:
             outs = self._run(True)
         finally:
             self.net._stage_cut = False
         logs, loss, heads, loss_smooth = self._losses(outs, True)
-        roots, grads = [h for h, _ in heads], [g for _, g in heads]
-        if torch.is_tensor(loss_smooth) and loss_smooth.requires_grad:
-            roots.append(loss_smooth)
-            grads.append(torch.ones_like(loss_smooth))
+        roots, grads = _backward_roots(heads, loss_smooth)
         raw = [r for r, _ in self.net._feats]                # l1..l4 as the encoder stages produced them
         cuts = [c for _, c in self.net._feats]               # ... and the leaves their consumers read
         # (nothing may keep this step's autograd graph alive into the next one: its AccumulateGrad nodes carry the stream
         # they were created on, and a node of an eager step re-used under a later stream capture breaks the capture)
         self.net._feats = None
-        self._staged_out = ({k: (v.detach() if torch.is_tensor(v) else v) for k, v in logs.items()},
-                            loss.detach() if torch.is_tensor(loss) else loss)
+        self._staged_out = _detached(logs, loss)
 
         def finish(si, idx, got):
-            opt.gather_stage(idx, got, skip=skip, attach=True, prezeroed=bool(plan is not None and plan.vecs))
+            opt.gather_stage(idx, got, attach=True, **WeightPlan.gather_args())
             if plan is not None and idx:
                 lo = opt._spans[idx[0]][0]
                 hi = opt._spans[idx[-1]][0] + opt._spans[idx[-1]][1]
@@ -647,52 +656,40 @@ class _DepthBase(SingleStageModel):
         rest of the backward pass -- the 610 MB of InstaDepthNet_od's gradients are on the wire while the encoder's
         backward (most of the pass) still runs.  Second step of a shape: one hipGraph PER STAGE, replayed afterwards with
         the collectives launched in between (as the ResNet nets do); identical kernels and order, bit-identical results."""
-        from . import ops
         if self._buckets is None:
             self._buckets = distributed_utils.GradientBuckets(self)
         bk = self._buckets
         key = (tuple(self.rgb.shape), self.rgb.data_ptr(), self.PAIR_MODE, self.optim.flat_params.data_ptr())
         graphs_ok = self._use_graph and not engine.prof_active()
-        if graphs_ok and self._dp_graphs is not None and self._dp_key == key:
-            for si, g in enumerate(self._dp_graphs):
-                g.replay()
-                bk.launch(si)
-            bk.finish()
-            logs, loss = self._dp_out
-            return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in logs.items()}, loss.clone()
-        plan = self._wplan if (self._wplan and self.PAIR_MODE and self._wplan.dtype == self.net._act_dtype()) else None
-        recording = self._wplan is None and self.PAIR_MODE and hasattr(self.optim, "_spans")
-        capture = graphs_ok and self._seen_key == key and not recording
-        graphs = None
-        if capture:
+        graphs = self._dp_graphs if (graphs_ok and self._dp_key == key) else None
+        if graphs is None and graphs_ok and self._seen_key == key and not self._live_plan()[1]:
             # only the capture sits in the try-block: no collective has been launched yet, so falling back is safe
             try:
                 torch.cuda.synchronize()
-                ops.WeightPlan.active = plan
-                gen = self._staged_steps(plan)
-                graphs = []
-                for si in range(bk.num_stages):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None, capture_error_mode="thread_local"):
-                        if si == 0 and plan is not None:
-                            plan.prepare()
-                        assert next(gen) == si
-                    graphs.append(g)
-                gen.close()
+                with self._plan_step(prepare=False) as plan:     # (prepare() belongs into stage 0's graph)
+                    gen = self._staged_steps(plan)
+                    graphs = []
+                    for si in range(bk.num_stages):
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None,
+                                              capture_error_mode="thread_local"):
+                            if si == 0 and plan is not None:
+                                plan.prepare()
+                            assert next(gen) == si
+                        graphs.append(g)
+                    gen.close()
             except Exception as ex:   # noqa: BLE001 -- capture unsupported here: stay eager
                 graphs = None
                 self._use_graph = False
                 print("instaorder_amd: per-stage hipGraph capture of the MiDaS step disabled (%s)" % ex)
-            finally:
-                ops.WeightPlan.active = None
+            else:
+                self._dp_graphs, self._dp_key, self._dp_out = graphs, key, self._staged_out
         if graphs is not None:
-            self._dp_graphs, self._dp_key, self._dp_out = graphs, key, self._staged_out
             for si, g in enumerate(graphs):
                 g.replay()
                 bk.launch(si)
             bk.finish()
-            logs, loss = self._dp_out
-            return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in logs.items()}, loss.clone()
+            return _cloned(*self._dp_out)
         # eager (first step of a shape, profiling, graphs disabled)
         out = self._staged_fwd_bwd(bk.launch)
         bk.finish()
@@ -702,23 +699,10 @@ class _DepthBase(SingleStageModel):
     def _staged_fwd_bwd(self, on_stage=None):
         """One pass of ``_staged_steps`` with the filter plan prepared / recorded around it; ``on_stage(si)`` is called as
         soon as stage si's slice of the flat gradient buffer is final (the data-parallel step launches its all-reduce)."""
-        from . import ops
-        plan = self._wplan if (self._wplan and self.PAIR_MODE and self._wplan.dtype == self.net._act_dtype()) else None
-        recording = self._wplan is None and self.PAIR_MODE and hasattr(self.optim, "_spans")
-        if recording:
-            ops.WeightPlan.start_recording()
-        if plan is not None:
-            plan.prepare()
-        ops.WeightPlan.active = plan
-        try:
+        with self._plan_step() as plan:
             for si in self._staged_steps(plan):
                 if on_stage is not None:
                     on_stage(si)
-        finally:
-            ops.WeightPlan.active = None
-            recs = ops.WeightPlan.stop_recording() if recording else None
-        if recording:
-            self._wplan = ops.WeightPlan(self.optim, recs, self.net._act_dtype()) if recs else False
         return self._staged_out
 
     def step(self):
@@ -744,8 +728,7 @@ class _DepthBase(SingleStageModel):
         key = (tuple(self.rgb.shape), self.rgb.data_ptr(), self.PAIR_MODE, self.optim.flat_params.data_ptr())
         if self._use_graph and self._graph is not None and self._graph_key == key and not engine.prof_active():
             self._graph.replay()
-            logs, loss = self._graph_out
-            logs, loss = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in logs.items()}, loss.clone()
+            logs, loss = _cloned(*self._graph_out)
         elif self._use_graph and self._seen_key == key and not engine.prof_active():
             # second step with this shape (the first ran eagerly and warmed every kernel): capture, then run it
             try:
@@ -756,7 +739,7 @@ class _DepthBase(SingleStageModel):
                     logs, loss = self._fwd_loss_bwd()
                 self._graph, self._graph_key, self._graph_out = g, key, (logs, loss)
                 g.replay()
-                logs, loss = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in logs.items()}, loss.clone()
+                logs, loss = _cloned(logs, loss)
             except Exception as ex:   # noqa: BLE001 -- capture unsupported here: stay eager
                 self._use_graph = False
                 self._graph = None

@@ -569,6 +569,51 @@ def test_batch_norm_node(dtype, G, R):
     _chk(tag + " didentity", _cpu(idt.grad), ir.grad, 1e-6)
 
 
+def test_plan_with_vectors_but_no_filters_clears_the_flat_buffer(monkeypatch):
+    """An ops.WeightPlan that holds directly written BatchNorm gradients and NO filter (a module of BatchNorm layers alone):
+    its prepare() still clears the flat gradient buffer, and only because it did are gather_grads told ``prezeroed`` -- a
+    parameter no loss reaches delivers zero, not what the buffer held before; dgamma / dbeta are the values the autograd +
+    gather route (IO_DEPTH_DIRECT_GRADS=0) delivers, bit for bit (the same kernel writing to another destination)."""
+    from instaorder_amd import midas_net, ops, optim
+    N, H, C = 4, 6, 128
+    gen = torch.Generator().manual_seed(731)
+    x = _dev(torch.randn(N, C, H, H, generator=gen, dtype=torch.float64) * 0.6 + 0.3, torch.float32)
+    dout = _dev(torch.randn(N, C, H, H, generator=gen, dtype=torch.float64), torch.float32)
+    g64, b64 = torch.rand(C, generator=gen, dtype=torch.float64) + 0.5, torch.randn(C, generator=gen, dtype=torch.float64)
+
+    def step(mod, opt, plan, record):
+        for p in opt._params:
+            p.grad = None
+        built = []
+        with ops.WeightPlan.step(plan, opt if record else None, torch.float32, built.append):
+            mod.bn(x).backward(dout)
+            opt.gather_grads(**ops.WeightPlan.gather_args())
+            if plan is not None:
+                plan.unpack_grads()
+        return built[0] if record else None
+
+    res = {}
+    for direct in ("1", "0"):
+        monkeypatch.setenv("IO_DEPTH_DIRECT_GRADS", direct)
+        mod = nn.Module()
+        mod.bn, mod.unused = midas_net.BatchNorm2d(C), nn.Parameter(torch.ones(70))
+        with torch.no_grad():
+            mod.bn.weight.copy_(g64)
+            mod.bn.bias.copy_(b64)
+        mod.to(DEV).train()
+        opt = optim.FlatSGD(mod, lr=0.1)
+        plan = step(mod, opt, None, True)
+        assert plan and plan.n == 0 and len(plan.vecs) == (2 if direct == "1" else 0)
+        opt.flat_grads.fill_(7.0)                  # the unused parameter's slice and both BatchNorm slices
+        step(mod, opt, plan, False)
+        torch.cuda.synchronize()
+        res[direct] = [opt.flat_grads[opt.offset_of(p):][:p.numel()].clone() for p in (mod.unused, mod.bn.weight, mod.bn.bias)]
+        assert not plan.cleared                    # (the answer of prepare() does not outlive the step's bracket)
+    assert torch.equal(res["1"][0], torch.zeros(70, device=DEV)), res["1"][0][:4]
+    assert float(res["0"][1].abs().max()) > 0 and float(res["0"][2].abs().max()) > 0
+    assert torch.equal(res["1"][1], res["0"][1]) and torch.equal(res["1"][2], res["0"][2])
+
+
 # ---- 3. midas_net.Bottleneck and FeatureFusionBlock as modules ------------------------------------------------------------
 class _RefF(object):
     """torch.nn.functional for midas_oracle, with the HIP forward's ReLU masks (in call order) and rounding to the stored
