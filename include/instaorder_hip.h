@@ -940,6 +940,38 @@ int io_png_decode_par(const uint8_t* pool_dev, size_t pool_bytes, const io_png_d
                       int n, uint8_t* out, size_t out_bytes, void* workspace, size_t workspace_bytes, int32_t* status_dev,
                       int chunk_bytes, int32_t* info_dev, hipStream_t stream);
 
+/* ---- PCNet-M (UNet) inference, NHWC fp32 (csrc/unet.hip; instaorder_amd/unet.py) ------------------------------------
+ * Every entry point validates before anything is enqueued and writes nothing when it returns an error.
+ *
+ * io_conv3x3_co32_fwd: y = [relu](conv3x3(x, w) + bias[o]), stride 1, pad 1, exactly 32 output channels, on the fp32 matrix
+ * instructions (exact fp32 products).  Cin is the STORED input width: 8 (the packed network input), 32, 64 or 128; any
+ * N, H, W >= 1.  The filter operand is [9 taps][Cin][32] (tap = 3 r + s), an eval-mode BatchNorm folded in by the caller. */
+int io_conv3x3_co32_fwd(const float* x, const float* w_packed, const float* bias, float* y, int N, int H, int W, int Cin,
+                        int Cout, int relu, hipStream_t stream);
+/* Route switch read by instaorder_amd/unet.py (the library only keeps it): 1 (default; IO_UNET_CO32=0 in the environment
+ * starts it at 0) = the 32-channel layers run io_conv3x3_co32_fwd, 0 = they run io_conv2d_fwd_bias_dt with Cout padded to 64.
+ * io_set_unet_co32 returns the previous value. */
+int io_set_unet_co32(int on);
+int io_get_unet_co32(void);
+/* nn.MaxPool2d(2): out[N][H/2][W/2][C]; H and W even, C % 4 == 0; no indices */
+int io_maxpool2x2_fwd(const float* x, int N, int H, int W, int C, float* out, hipStream_t stream);
+/* The input of a UNet `up` block in one pass: out[n][y][x][0..C2) = x2[n][y][x][:], out[n][y][x][C2..C2+C1) = the bilinear x2
+ * upsampling (align_corners=True) of x1 at (y, x).  x2: [N][2h][2w][C2], x1: [N][h][w][C1]; C1 % 4 == C2 % 4 == 0. */
+int io_up2x_concat_fwd(const float* x2, const float* x1, int N, int h, int w, int C2, int C1, float* out, hipStream_t stream);
+/* out[p][pix][0] = (erase && m2 == 1 ? 0 : m1[p][pix]) * (scale ? scale[p] : 1), out[p][pix][1] = m2[p][pix], channels
+ * 2..Cs) = 0: the (target, eraser) planes of P patches of HW pixels as the first convolution reads them (Cs % 4 == 0). */
+int io_unet_pack_input(const float* m1, const float* m2, const float* scale, int P, int HW, int Cs, int erase, float* out,
+                       hipStream_t stream);
+/* The network head on act[P][HW][Cs]: logits l = wo[2][Cs] . act + bo[2]; comp (uint8, may be NULL) = softmax(l)[1] > th,
+ * evaluated as l1 - l0 > ln(th / (1 - th)); counts[p] (int32, may be NULL; zeroed here, integer atomics) = pixels with
+ * comp > (m2 == 1 ? 0 : m1) and m2 == 1; logits[P][HW][2] when not NULL.  Loss mode (target, partials and loss_sums all
+ * given): loss_sums[0] / [1] = the sum of the cross-entropy terms over the pixels with m2 != 0 / m2 == 0, target uint8 in
+ * {0, 1}; per-block partials (io_unet_head_partial_floats floats) added in a fixed order, so two runs agree bit for bit. */
+size_t io_unet_head_partial_floats(int P, int HW);
+int io_unet_head(const float* act, const float* wo, const float* bo, const float* m1, const float* m2, const uint8_t* target,
+                 int P, int HW, int Cs, float th, uint8_t* comp, int32_t* counts, float* logits, float* partials,
+                 size_t partial_floats, float* loss_sums, hipStream_t stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of every launch, per kernel class, on the launch
  * stream.  Process-global; io_prof_end synchronises on the recorded events and returns the number of
  * classes written.  flops / bytes are the ALGORITHMIC figures of the timed launches (the direct convolution's count). */

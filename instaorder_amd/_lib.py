@@ -287,6 +287,18 @@ SIGNATURES = {
     "io_instance_depth_select_workspace_bytes": (_Z, [_I, _I, _I]),
     # disp, H, W, masks, n, method, value, lo, hi, k, workspace, workspace_bytes, stream
     "io_instance_depth_select": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    # x, w_packed [9][Cin][32], bias, y, N, H, W, Cin, Cout (32), relu, stream
+    "io_conv3x3_co32_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "io_set_unet_co32": (_I, [_I]),
+    "io_get_unet_co32": (_I, []),
+    "io_maxpool2x2_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    # x2 [N][2h][2w][C2], x1 [N][h][w][C1], N, h, w, C2, C1, out, stream
+    "io_up2x_concat_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    # m1, m2, scale, P, HW, Cs, erase, out, stream
+    "io_unet_pack_input": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "io_unet_head_partial_floats": (_Z, [_I, _I]),
+    # act, wo, bo, m1, m2, target, P, HW, Cs, th, comp, counts, logits, partials, partial_floats, loss_sums, stream
+    "io_unet_head": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _Z, _P, _P]),
     "io_prof_begin": (_I, []),
     "io_prof_begin_ex": (_I, [_I]),
     "io_prof_end": (_I, [C.POINTER(ProfEntry), _I]),

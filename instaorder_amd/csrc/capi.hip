@@ -215,7 +215,7 @@ const char* kProfNames[IO_PROF_NCLASS] = {"conv_nt_kernel<128,false>", "conv_nt_
     "bn_apply", "bn_bwd", "pool_head", "filter_transpose", "pack_planes", "order_loss", "sgd_momentum",
     "conv_nt_kernel<wino>", "conv_wgrad_kernel<wino>", "adam", "grad_norm", "rle_decode", "poly_fill",
     "jpeg_entropy", "jpeg_idct", "jpeg_colour", "jpeg_prog_entropy", "png_inflate", "png_unfilter", "png_pack",
-    "png_par_search", "png_par_count", "png_par_store", "png_par_resolve"};
+    "png_par_search", "png_par_count", "png_par_store", "png_par_resolve", "conv3x3_co32", "unet_misc"};
 hipEvent_t prof_event() {
     if (!g_prof_pool.empty()) { hipEvent_t e = g_prof_pool.back(); g_prof_pool.pop_back(); return e; }
     hipEvent_t e;

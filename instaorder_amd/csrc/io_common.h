@@ -323,7 +323,7 @@ enum IoProfClass {
     IO_PROF_LOSS, IO_PROF_SGD, IO_PROF_CONV_WINO, IO_PROF_WGRAD_WINO, IO_PROF_ADAM, IO_PROF_GRAD_NORM,
     IO_PROF_RLE, IO_PROF_POLY, IO_PROF_JPEG_ENTROPY, IO_PROF_JPEG_IDCT, IO_PROF_JPEG_COLOUR, IO_PROF_JPEG_PROG_ENTROPY,
     IO_PROF_PNG_INFLATE, IO_PROF_PNG_UNFILTER, IO_PROF_PNG_PACK, IO_PROF_PNG_PAR_SEARCH, IO_PROF_PNG_PAR_COUNT,
-    IO_PROF_PNG_PAR_STORE, IO_PROF_PNG_PAR_RESOLVE, IO_PROF_NCLASS
+    IO_PROF_PNG_PAR_STORE, IO_PROF_PNG_PAR_RESOLVE, IO_PROF_UNET_CO32, IO_PROF_UNET, IO_PROF_NCLASS
 };
 struct IoProfScope {
     int idx;

@@ -57,14 +57,15 @@ def _gather_rows(rows, n_total, world_size):
 
 
 def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all", zd=0, disp_select_method="",
-             gt_ordering="ann", world_size=1, rank=0, return_orders=False, mask_rules="host"):
+             gt_ordering="ann", world_size=1, rank=0, return_orders=False, mask_rules="host", order_th=0.5):
     """Dispatch of ``Tester.run`` on ``data_cfg['trainval_dataset']``.  ``order_method``: one of the method strings of
     tools/test.py -- the network methods, or the annotation-free baselines 'area' / 'yaxis' (tools/test.py:306-318,
     421-433) -- or a callable ``(modal_masks, dataset_name) -> order matrix`` (any other model-free rule).  Returns a dict with 'recall', 'precision', 'f1'
     (occlusion datasets) and / or 'WHDR_<ovl>_<eq>' (depth datasets), plus 'num_test_images'; with ``return_orders``
     also 'orders' = {image index: (occlusion matrix | None, depth matrix | None)} of this rank's images.
     ``mask_rules='device'``: pair selection, the 'area' / 'yaxis' baselines, ``infer_gt_order`` and the disparity
-    selection run through ``instaorder_amd.mask_rules`` (same results); 'host' (the default) keeps the host loops."""
+    selection run through ``instaorder_amd.mask_rules`` (same results); 'host' (the default) keeps the host loops.
+    ``order_th``: the completion threshold of order_method='PartialCompletionMask' (tools/test.py ``--order_th``)."""
     rules = infer._mask_rules(mask_rules) or infer          # the module whose mask rules this run uses
     kind = data_cfg["trainval_dataset"]
     want_occ = kind in ("SupOcclusionOrderDataset", "PartialCompDataset", "SupDepthOccOrderDataset")
@@ -86,7 +87,8 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
                 modal = modal.to_dense()
         elif kind != "SupDepthOccOrderDataset" and data_cfg.get("use_category", False):
             modal = modal * category[:, None, None]
-        image = None if (callable(order_method) or order_method in ("area", "yaxis")) else _loaded(load_image(image_fn))
+        image = None if (callable(order_method) or order_method in ("area", "yaxis", "PartialCompletionMask")) \
+            else _loaded(load_image(image_fn))          # (PCNet-M reads masks only: use_rgb is False)
         boxes = expand_bbox(bboxes, data_cfg["enlarge_box"])
         gt_occ = gt_dep = None
         if want_occ:
@@ -130,6 +132,10 @@ def evaluate(model, data_reader, load_image, data_cfg, order_method, pairs="all"
             elif order_method == "yaxis":   # :429-433
                 pred_occ = rules.infer_occ_order_yaxis(modal, occluder="lower" if dataset in ("COCOA", "InstaOrder")
                                                        else "higher")
+            elif order_method == "PartialCompletionMask":      # tools/test.py:435-439
+                pred_occ = infer.infer_order(model, image, modal, category, boxes, pairs=pairs, use_rgb=False, th=order_th,
+                                             dilate_kernel=0, input_size=256, min_input_size=16, interp="nearest",
+                                             debug_info=False, mask_rules=mask_rules)
             elif order_method in ("InstaOrderNet_o", "OrderNet"):
                 pred_occ = infer.infer_order_sup_occ(model, image, modal, boxes, pairs, order_method, mode, size,
                                                      mask_rules=mask_rules)

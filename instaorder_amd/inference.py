@@ -458,6 +458,92 @@ def infer_order_sup_occ_depth(model, image, inmodal, bboxes, pairs, method, patc
     return res["occ_order"], res["depth_order"]
 
 
+def order_from_occ_values(occ_value):
+    """inference.py:682-684, literally: where [i, j] > [j, i] the entry is written 0, where [i, j] < [j, i] it is written
+    1, and pairs with both values 0 are written 0 -- so [i, j] = 1 says that the completion of i under j's mask is the
+    SMALLER one, i.e. i is the occluder."""
+    occ_value = np.asarray(occ_value)
+    n = occ_value.shape[0]
+    order = np.zeros((n, n), dtype=np.int64)
+    order[occ_value > occ_value.transpose()] = 0
+    order[occ_value < occ_value.transpose()] = 1
+    order[(occ_value == 0) & (occ_value == 0).transpose()] = 0
+    return order
+
+
+def infer_order(model, image, inmodal, category, bboxes, pairs, use_rgb=False, th=0.5, dilate_kernel=0, input_size=None,
+                min_input_size=32, interp='nearest', debug_info=False, max_pairs=64, mask_rules="host"):
+    """PCNet-M order recovery by dual completion (reference inference.py:627-688), all ordered pairs of the image in
+    batches of ``max_pairs`` patches: ``order_from_occ_values(infer_occ_values(...))``.  ``debug_info=True``: the
+    reference's (order_matrix, ind, inmodal_patches, eraser_patches, amodal_patches) with uint8 patches.  ``image`` is not
+    read (use_rgb=False is the only mode), and ``min_input_size`` only matters with input_size=None."""
+    if use_rgb:
+        raise NotImplementedError("infer_order: use_rgb=True is not in the package (the reference's UNet takes no image).")
+    if input_size is None:
+        raise NotImplementedError("infer_order: input_size=None (every box at its own size) is not in the package.")
+    if interp != 'nearest':
+        raise NotImplementedError("infer_order: interp=%r is not in the package (only 'nearest')." % (interp,))
+    if dilate_kernel > 0:
+        raise NotImplementedError("infer_order: dilate_kernel=%r is not in the package (only 0)." % (dilate_kernel,))
+    occ_value, ind, pats = infer_occ_values(model, inmodal, category, bboxes, pairs, th, input_size, debug_info, max_pairs,
+                                            mask_rules)
+    order = order_from_occ_values(occ_value)
+    if len(ind) == 0 or not debug_info:          # inference.py:642-643: no pair, no tuple
+        return order
+    return (order, ind) + tuple(pats)
+
+
+def infer_occ_values(model, inmodal, category, bboxes, pairs, th=0.5, input_size=256, keep_patches=False, max_pairs=64,
+                     mask_rules="host"):
+    """The float32 ``occ_value`` matrix of ``infer_order`` -> (occ_value, ind [P, 2], patches | None).  For every selected
+    pair (i, j), in the reference's order [i, j], [j, i]: the target tid and the eraser eid are cropped by the TARGET's
+    box and nearest-resized to ``input_size`` (datasets.PairRenderer, masks kept encoded); the target is erased under the
+    eraser and multiplied by ``category[tid]`` on the way into the network (io_unet_pack_input); the head thresholds
+    softmax[1] > th and counts the pixels with completion > erased target and eraser == 1 (io_unet_head).
+    ``occ_value[tid, eid] = count * (bboxes[tid, 2] / input_size) ** 2``: an integer times a float64, stored as float32,
+    as the reference forms it.  One copy brings all counts back.  ``keep_patches``: lists of the uint8 erased targets,
+    erasers and completions.  Patches are independent, so the chunk size ``max_pairs`` does not change a bit."""
+    input_size = int(input_size)
+    if input_size <= 0 or input_size % 16 != 0:
+        raise ValueError("infer_order: input_size=%d must be a positive multiple of 16 (the UNet pools four times and "
+                         "joins the skip tensors without padding)" % input_size)
+    max_pairs = int(max_pairs)
+    if max_pairs < 1:
+        raise ValueError("infer_order: max_pairs must be at least 1")
+    mr = _mask_rules(mask_rules)
+    inmodal = _host_masks(inmodal, mr)
+    pair_list = _select_pairs(mr, inmodal, pairs)
+    num = int(inmodal.shape[0])
+    occ_value = np.zeros((num, num), dtype=np.float32)
+    ind = np.array([d for i, j in pair_list for d in ([i, j], [j, i])], dtype=np.int64).reshape(-1, 2)
+    if len(ind) == 0:
+        return occ_value, ind, None
+    bboxes = np.asarray(bboxes)
+    net = model.net
+    dev = next(net.parameters()).device
+    modal = inmodal if _is_rle(inmodal) else np.ascontiguousarray(np.asarray(inmodal).astype(np.uint8))
+    r = _renderer(dev, input_size)
+    scale_all = torch.as_tensor(np.asarray(category)[ind[:, 0]].astype(np.float32)).to(dev)
+    counts, keep = [], ([], [], [])
+    for lo in range(0, len(ind), max_pairs):
+        rows = ind[lo:lo + max_pairs]
+        # (the interpolation code of an item is the picture's; mask planes are always nearest)
+        items = [(0, int(t), int(e), tuple(int(v) for v in bboxes[t]), 1, False) for t, e in rows]
+        _, m1, m2 = r.render([None], [modal], items, load_rgb=False)
+        with torch.no_grad():
+            out = net.run(m1[:, 0], m2[:, 0], scale=scale_all[lo:lo + len(rows)].contiguous(), erase=True, th=th)
+        counts.append(out["counts"])
+        if keep_patches:
+            keep[0].append(torch.where(m2[:, 0] == 1, torch.zeros_like(m1[:, 0]), m1[:, 0]).to(torch.uint8))
+            keep[1].append(m2[:, 0].to(torch.uint8))
+            keep[2].append(out["comp"])
+    counts = torch.cat(counts).cpu().numpy().astype(np.int64)
+    for k, (t, e) in enumerate(ind):
+        occ_value[t, e] = counts[k] * ((bboxes[t, 2] / float(input_size)) ** 2)
+    pats = [list(torch.cat(k).cpu().numpy()) for k in keep] if keep_patches else None
+    return occ_value, ind, pats
+
+
 def _matrices(n, pairs, dec, want_occ):
     occ = np.zeros((n, n), dtype=np.int64)
     dep = np.zeros((n, n), dtype=np.int64)

@@ -10,10 +10,11 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import common_utils, distributed_utils, midas_net, resnet_cls
+from . import common_utils, distributed_utils, midas_net, resnet_cls, unet
 from .optim import FlatAdam, FlatSGD, FusedAdam, FusedSGD
 
-_BACKBONES = {"resnet50_cls": resnet_cls.resnet50_cls}
+_BACKBONES = {"resnet50_cls": resnet_cls.resnet50_cls, "unet025": unet.unet025, "unet05": unet.unet05, "unet1": unet.unet1,
+              "unet2": unet.unet2, "unet4": unet.unet4}
 
 
 class SingleStageModel(object):
