@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, arena, jpeg, png, poly, rle
 from .jpeg import is_jpeg
 from .png import is_png
 from .rle import is_encoded
@@ -88,7 +88,7 @@ class PairRenderer(object):
         self._pinned = [None, None]
         self._events = [None, None]
         self._turn = 0
-        self._status = [None, None]  # per staging slot: [(pinned int32 status words of a JPEG / PNG decode, the images, jpeg / png)]
+        self._status = [None, None]  # per staging slot: [(pinned int32 status words of a JPEG / PNG decode, its arena.Group)]
         self.last_upload = None      # bytes the last render() sent to the device: images / masks (or run tables, vertices) / descriptors
 
     def _staging(self, nbytes):
@@ -107,8 +107,8 @@ class PairRenderer(object):
         if self._status[k] is not None:
             pending = self._status[k]
             self._status[k] = None
-            for words, images, codec in pending:
-                codec.raise_for_status(words.numpy(), images)
+            for words, g in pending:
+                g.raise_for_status(words.numpy(), g.images)
 
     def check_status(self):
         """Waits for the batches still in flight and raises RuntimeError naming a JPEG or PNG image that did not decode.  render()
@@ -132,33 +132,13 @@ class PairRenderer(object):
                                                                                images[ii].shape))
         return n, H, W
 
-    @staticmethod
-    def _fill_desc(d, image_off, mask1_off, mask2_off, H, W, box, interp, flip):
-        d.image_off, d.mask1_off, d.mask2_off = image_off, mask1_off, mask2_off
-        d.H, d.W = H, W
-        d.x, d.y, d.w, d.h = [int(v) for v in box]
-        d.flip = int(bool(flip))
-        d.interp = int(interp)
-
-    @staticmethod
-    def _fill_stage(host, images, masks, placed):
-        """placed: (key, offset) of every image ("img", ii) and dense mask ("m", ii, i) that is uploaded"""
-        for key, o in placed:
-            src = images[key[1]] if key[0] == "img" else masks[key[1]][key[2]]
-            host[o:o + src.size] = np.ascontiguousarray(src).reshape(-1)
-
-    def _upload_done(self, slot, stream):
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        self._events[slot] = ev
-
-    def _launch(self, arena, nbytes, desc_dev, desc, load_rgb, stream):
+    def _planes(self, arena_dev, nbytes, desc_dev, desc, load_rgb, stream):
         P, S, SH = len(desc), self.S, self.SH
         rgb = torch.empty((P, 3, SH, S), device=self.device) if load_rgb else None
         m1 = torch.empty((P, 1, SH, S), device=self.device)
         m2 = torch.empty((P, 1, SH, S), device=self.device)
         rc = _lib.lib().io_pair_planes_u8_hw(
-            C.c_void_p(arena), C.c_size_t(nbytes), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p), P, SH, S,
+            C.c_void_p(arena_dev), C.c_size_t(nbytes), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p), P, SH, S,
             C.cast(self.mean, C.c_void_p), C.cast(self.std, C.c_void_p),
             C.c_void_p(rgb.data_ptr()) if load_rgb else None, C.c_void_p(m1.data_ptr()), C.c_void_p(m2.data_ptr()),
             C.c_void_p(stream.cuda_stream))
@@ -168,210 +148,121 @@ class PairRenderer(object):
         return rgb, m1, m2
 
     def render(self, images, masks, items, load_rgb=True):
-        """images: list of uint8 [H,W,3] arrays, ``jpeg.JpegImage`` or 8-bit ``png.PngImage`` (entries may be None when load_rgb is False); masks: list of uint8
-        [n,H,W] arrays, ``rle.RLEMasks`` or ``poly.PolyMasks``, one per image; items: list of (image_index, idx1, idx2,
-        (x, y, w, h), interp, flip)."""
+        """images: list of uint8 [H,W,3] arrays, ``jpeg.JpegImage`` or 8-bit ``png.PngImage`` (entries may be None when
+        load_rgb is False); masks: list of uint8 [n,H,W] arrays, ``rle.RLEMasks`` or ``poly.PolyMasks``, one per image;
+        items: list of (image_index, idx1, idx2, (x, y, w, h), interp, flip).
+
+        Every referenced image and mask gets one slot of a device arena: an array is uploaded into it, an encoded one
+        is decoded into it by the ``arena.Group`` of its codec (``rle``, ``poly``, ``jpeg`` baseline, ``png``, ``jpeg``
+        progressive).  The arena, in this order:
+
+          1. the uploaded arrays
+          2. the blobs of each group (run tables, vertices, entropy bytes, ..., and their descriptors)
+          3. the pair descriptors
+          4. the decoded slots
+          5. the workspace of each group
+          6. the status words of each group
+
+        1 to 3 come through the pinned staging buffer in one copy.  Then one library call per group with members fills
+        its slots -- baseline JPEG, PNG, progressive JPEG, run-length, polygon -- and ``io_pair_planes_u8_hw`` reads the
+        arena.  A batch of arrays alone is the case in which every group is empty."""
         P = len(items)
         if P == 0:
             raise ValueError("PairRenderer.render: empty batch")
-        if any(is_encoded(m) for m in masks) or (load_rgb and any(is_jpeg(im) or is_png(im) for im in images)):
-            return self._render_rle(images, masks, items, load_rgb)
-        # arena layout: every referenced image once, every referenced mask once (16-byte aligned)
-        off, cursor = {}, 0
-        sent = {"img": 0, "m": 0}
-
-        def place(key, nbytes):
-            nonlocal cursor
-            if key not in off:
-                off[key] = cursor
-                cursor = (cursor + nbytes + 15) // 16 * 16
-                sent[key[0]] += nbytes
-            return off[key]
-
-        desc = (_lib.PairDesc * P)()
-        for k, (ii, i1, i2, box, interp, flip) in enumerate(items):
-            n, H, W = self._check_item(images, masks, ii, load_rgb)
-            image_off = place(("img", ii), H * W * 3) if load_rgb else 0
-            self._fill_desc(desc[k], image_off, place(("m", ii, int(i1)), H * W), place(("m", ii, int(i2)), H * W),
-                            H, W, box, interp, flip)
-        nbytes = max(cursor, 16)
-        dbytes = C.sizeof(desc)
-        slot, stage = self._staging(nbytes + dbytes)
-        host = stage.numpy()
-        self._fill_stage(host, images, masks, off.items())
-        host[nbytes:nbytes + dbytes] = np.frombuffer(desc, dtype=np.uint8)
-        dev = stage[:nbytes + dbytes].to(self.device, non_blocking=True)
-        stream = torch.cuda.current_stream(self.device)
-        self._upload_done(slot, stream)
-        self.last_upload = dict(images=sent["img"], masks=sent["m"], descriptors=dbytes, total=nbytes + dbytes)
-        return self._launch(dev.data_ptr(), nbytes, dev.data_ptr() + nbytes, desc, load_rgb, stream)
-
-    def _render_rle(self, images, masks, items, load_rgb):
-        """render() for a batch in which at least one image carries ``rle.RLEMasks`` or ``poly.PolyMasks``, or is a
-        ``jpeg.JpegImage`` or a ``png.PngImage``.  The arena lives on the device and only part of it is uploaded: one device buffer [array images
-        and dense masks | run tables | decode descriptors | vertices | part and mask descriptors | entropy bytes | JPEG
-        tables and descriptors | PNG stream bytes and descriptors | tables, scans and bytes of progressive JPEG files | pair descriptors | decoded masks and images | polygon
-        workspace | JPEG workspace and status | PNG workspace and status | progressive JPEG workspace and status], of which everything before the decoded part comes through the pinned staging buffer in one copy.  One
-        ``io_rle_decode_u8`` launch fills the slot of every referenced run-length mask, one ``io_poly_fill_u8`` call the
-        slot of every referenced polygon instance and one ``io_jpeg_decode_u8`` call the slot of every referenced JPEG
-        image (one ``io_jpeg_decode_prog_u8`` call those of the progressive ones) and one ``io_png_decode`` call the slot of every referenced PNG image, then ``io_pair_planes_u8_hw`` runs on the arena as it does for dense arrays.  (A batch without polygons,
-        JPEG or PNG images has empty regions for them: the layout of the run-length path as it was.)"""
-        from . import jpeg, png, poly, rle
-        P = len(items)
-        up, dec = {}, {}                     # key -> offset inside its region
-        cursors = {id(up): 0, id(dec): 0}
-        sent = {"img": 0, "m": 0}
+        up, dec, off = arena.Layout(), arena.Layout(), {}           # the regions 1 and 4; key -> (region, offset in it)
+        sent = dict(images=0, masks=0, descriptors=0)
 
         def place(region, key, nbytes):
-            if key not in region:
-                region[key] = cursors[id(region)]
-                cursors[id(region)] = (cursors[id(region)] + nbytes + 15) // 16 * 16
+            if key not in off:
+                off[key] = (region, region.add(nbytes))
                 if region is up:
-                    sent[key[0]] += nbytes
+                    sent["images" if key[0] == "img" else "masks"] += nbytes
             return key
 
         keys = []
         for ii, i1, i2, box, interp, flip in items:
             n, H, W = self._check_item(images, masks, ii, load_rgb)
             region = dec if is_encoded(masks[ii]) else up
-            keys.append((place(dec if is_jpeg(images[ii]) or is_png(images[ii]) else up, ("img", ii), H * W * 3) if load_rgb else None, region,
+            keys.append((place(dec if is_jpeg(images[ii]) or is_png(images[ii]) else up, ("img", ii), H * W * 3)
+                         if load_rgb else None,
                          place(region, ("m", ii, range(n)[int(i1)]), H * W),
                          place(region, ("m", ii, range(n)[int(i2)]), H * W)))
-        # an instance of the decoded region is a run-length code (of RLEMasks, or one inside PolyMasks) or a polygon
-        refs = [(key, (masks[key[1]], key[2]) if isinstance(masks[key[1]], rle.RLEMasks) else masks[key[1]].rle_ref(key[2]))
-                for key in dec if key[0] == "m"]
-        jp_keys = [key for key in dec if key[0] == "img" and is_jpeg(images[key[1]]) and not images[key[1]].progressive]
-        # progressive files: a second descriptor group, workspace and launch (io_jpeg_decode_prog_u8) behind the baseline one
-        pj_keys = [key for key in dec if key[0] == "img" and is_jpeg(images[key[1]]) and images[key[1]].progressive]
-        pj = jpeg.descriptors_progressive([images[k[1]] for k in pj_keys], [0] * len(pj_keys)) if pj_keys else None
-        pj_blobs = jpeg.progressive_blobs(pj) if pj_keys else []     # views: the offsets set below are seen through them
-        pg_keys = [key for key in dec if key[0] == "img" and is_png(images[key[1]])]
-        gpool, gdesc = png.descriptors([images[k[1]] for k in pg_keys], [0] * len(pg_keys)) if pg_keys else (
-            np.zeros(0, np.uint8), ())
-        gdbytes = C.sizeof(gdesc) if pg_keys else 0
-        jpool, jtabs, jdesc = jpeg.descriptors([images[k[1]] for k in jp_keys], [0] * len(jp_keys)) if jp_keys else (
-            np.zeros(0, np.uint8), np.zeros(0, np.uint8), ())
-        jdbytes = C.sizeof(jdesc) if jp_keys else 0
-        dec_keys = [key for key, ref in refs if ref is not None]
-        pol_keys = [key for key, ref in refs if ref is None]
-        ends, rdesc = rle.descriptors([ref for key, ref in refs if ref is not None], [0] * len(dec_keys))
-        verts, pparts, pmasks, n_parts = poly.descriptors([(masks[k[1]], k[2]) for k in pol_keys], [0] * len(pol_keys))
-        pbytes = (C.sizeof(pparts), C.sizeof(pmasks)) if pol_keys else (0, 0)
+
+        def image(key):
+            return images[key[1]]
+
+        def rle_ref(key):                    # a decoded instance is a run-length code (of RLEMasks, or one inside PolyMasks) or a polygon
+            m = masks[key[1]]
+            return (m, key[2]) if isinstance(m, rle.RLEMasks) else m.rle_ref(key[2])
+
+        dec_img = [key for key, (region, o) in off.items() if region is dec and key[0] == "img"]
+        dec_m = [key for key, (region, o) in off.items() if region is dec and key[0] == "m"]
+        members = [[k for k in dec_m if rle_ref(k) is not None],
+                   [k for k in dec_m if rle_ref(k) is None],
+                   [k for k in dec_img if is_jpeg(image(k)) and not image(k).progressive],
+                   [k for k in dec_img if is_png(image(k))],
+                   [k for k in dec_img if is_jpeg(image(k)) and image(k).progressive]]
+        groups = [rle.group([rle_ref(k) for k in members[0]]),
+                  poly.group([(masks[k[1]], k[2]) for k in members[1]]),
+                  jpeg.group([image(k) for k in members[2]]),       # the stages jpeg.set_entropy / png.set_inflate name
+                  png.group([image(k) for k in members[3]]),        # size the workspace and are the entry points called
+                  jpeg.group_progressive([image(k) for k in members[4]])]
         desc = (_lib.PairDesc * P)()
-        tab_at = max(cursors[id(up)], 16)
-        rd_at = tab_at + (ends.nbytes + 15) // 16 * 16
-        vt_at = rd_at + (C.sizeof(rdesc) + 15) // 16 * 16
-        pp_at = vt_at + (verts.nbytes + 15) // 16 * 16
-        pm_at = pp_at + (pbytes[0] + 15) // 16 * 16
-        jp_at = pm_at + (pbytes[1] + 15) // 16 * 16
-        jt_at = jp_at + (jpool.size + 15) // 16 * 16
-        jd_at = jt_at + (jtabs.size + 15) // 16 * 16
-        gp_at = jd_at + (jdbytes + 15) // 16 * 16
-        gd_at = gp_at + (gpool.size + 15) // 16 * 16
-        pj_at, pd_at = [], gd_at + (gdbytes + 15) // 16 * 16
-        for b in pj_blobs:
-            pj_at.append(pd_at)
-            pd_at += (b.size + 15) // 16 * 16
-        dec_at = pd_at + (C.sizeof(desc) + 15) // 16 * 16             # = the bytes that are uploaded
-        nbytes = dec_at + max(cursors[id(dec)], 16)
-        ws_at = (nbytes + 15) // 16 * 16
-        ws_bytes = poly.workspace_bytes(pparts, n_parts, pmasks) if pol_keys else 0
-        for k, key in enumerate(dec_keys):
-            rdesc[k].out_off = dec_at + dec[key]
-        for k, key in enumerate(pol_keys):
-            pmasks[k].out_off = dec_at + dec[key]
-        for k, key in enumerate(jp_keys):
-            jdesc[k].out_off = dec_at + dec[key]
-        for k, key in enumerate(pg_keys):
-            gdesc[k].out_off = dec_at + dec[key]
-        for k, key in enumerate(pj_keys):
-            pj["desc"][k].out_off = dec_at + dec[key]
-        jws_at = (ws_at + ws_bytes + 15) // 16 * 16
-        jent = jpeg.get_entropy()                                    # the stage jpeg.set_entropy names sizes the arena ...
-        jws_bytes = jpeg.workspace_bytes(jdesc, jent) if jp_keys else 0
-        st_at = jws_at + jws_bytes
-        end = st_at + 4 * len(jp_keys) if jp_keys else (ws_at + ws_bytes if pol_keys else nbytes)
-        gws_at = (end + 15) // 16 * 16
-        ginf = png.get_inflate()                                     # as above: the stage png.set_inflate names
-        gws_bytes = png.workspace_bytes(gdesc, ginf) if pg_keys else 0
-        gst_at = gws_at + gws_bytes
-        if pg_keys:
-            end = gst_at + 4 * len(pg_keys)
-        pws_at = (end + 15) // 16 * 16
-        pws_bytes = jpeg.workspace_bytes_progressive(pj) if pj_keys else 0
-        pst_at = pws_at + pws_bytes
-        if pj_keys:
-            end = pst_at + 4 * len(pj_keys)
-        for k, ((ii, i1, i2, box, interp, flip), (kimg, region, k1, k2)) in enumerate(zip(items, keys)):
-            base = dec_at if region is dec else 0
-            _, H, W = masks[ii].shape
-            image_off = 0 if not load_rgb else (dec_at + dec[kimg] if kimg in dec else up[kimg])
-            self._fill_desc(desc[k], image_off, base + region[k1], base + region[k2], H, W, box, interp,
-                            flip)
+        lay = arena.Layout()
+        lay.add(up.size)
+        ats = [[lay.add(b.size) for b in g.blobs] for g in groups]
+        pd_at = lay.add(C.sizeof(desc))
+        dec_at = lay.add(dec.size)                                   # = the bytes that are uploaded
+        nbytes = lay.size                                            # what the decoders may write, the render kernel read
+        for g, ks in zip(groups, members):
+            g.set_outs(dec_at + off[key][1] for key in ks)
+        ws_bytes = [g.workspace_bytes() for g in groups]
+        ws_at = [lay.add(b) for b in ws_bytes]
+        st_at = [lay.add(4 * g.n_status) for g in groups]
+
+        def where(key):
+            region, o = off[key]
+            return o if region is up else dec_at + o
+
+        for d, (ii, i1, i2, box, interp, flip), (kimg, k1, k2) in zip(desc, items, keys):
+            d.image_off, d.mask1_off, d.mask2_off = where(kimg) if load_rgb else 0, where(k1), where(k2)
+            _, d.H, d.W = masks[ii].shape
+            d.x, d.y, d.w, d.h = [int(v) for v in box]
+            d.flip, d.interp = int(bool(flip)), int(interp)
         slot, stage = self._staging(dec_at)
         host = stage.numpy()
-        self._fill_stage(host, images, masks, up.items())
-        host[tab_at:tab_at + ends.nbytes] = ends.view(np.uint8)
-        host[rd_at:rd_at + C.sizeof(rdesc)] = np.frombuffer(rdesc, dtype=np.uint8)
-        if pol_keys:
-            host[vt_at:vt_at + verts.nbytes] = verts.view(np.uint8).reshape(-1)
-            host[pp_at:pp_at + pbytes[0]] = np.frombuffer(pparts, dtype=np.uint8)
-            host[pm_at:pm_at + pbytes[1]] = np.frombuffer(pmasks, dtype=np.uint8)
-        if jp_keys:
-            host[jp_at:jp_at + jpool.size] = jpool
-            host[jt_at:jt_at + jtabs.size] = jtabs
-            host[jd_at:jd_at + jdbytes] = np.frombuffer(jdesc, dtype=np.uint8)
-        if pg_keys:
-            host[gp_at:gp_at + gpool.size] = gpool
-            host[gd_at:gd_at + gdbytes] = np.frombuffer(gdesc, dtype=np.uint8)
-        for a, b in zip(pj_at, pj_blobs):
-            host[a:a + b.size] = b
-        host[pd_at:pd_at + C.sizeof(desc)] = np.frombuffer(desc, dtype=np.uint8)
-        dev = torch.empty(end, dtype=torch.uint8, device=self.device)
+        for key, (region, o) in off.items():
+            if region is up:
+                src = images[key[1]] if key[0] == "img" else masks[key[1]][key[2]]
+                host[o:o + src.size] = np.ascontiguousarray(src).reshape(-1)
+        for g, at in zip(groups, ats):
+            arena.pack(g.blobs, at, host)
+        arena.pack([arena.as_bytes(desc)], [pd_at], host)
+        dev = torch.empty(lay.size, dtype=torch.uint8, device=self.device)
         dev[:dec_at].copy_(stage[:dec_at], non_blocking=True)
+        for g in groups:
+            for b, what in zip(g.blobs, g.classes):
+                sent[what] += b.size
+        sent["descriptors"] += C.sizeof(desc)
+        self.last_upload = dict(sent, total=dec_at)
         stream = torch.cuda.current_stream(self.device)
-        self._upload_done(slot, stream)
-        pj_sent = [b.size for b in pj_blobs] or [0] * 6              # tables, huff, desc, image, scan, pool
-        self.last_upload = dict(images=sent["img"] + jpool.size + jtabs.size + gpool.size + pj_sent[0] + pj_sent[1] + pj_sent[5],
-                                masks=sent["m"] + ends.nbytes + verts.nbytes,
-                                descriptors=C.sizeof(rdesc) + sum(pbytes) + jdbytes + gdbytes + sum(pj_sent[2:5]) + C.sizeof(desc),
-                                total=dec_at)
-        base = dev.data_ptr()
-        if jp_keys:
-            # ... and is the entry point called: io_jpeg_decode_u8 or io_jpeg_decode_par_u8
-            jpeg.launch(jent, base + jp_at, jpool.size, base + jt_at, jtabs, base + jd_at, jdesc, base, nbytes, base + jws_at,
-                        jws_bytes, base + st_at, stream.cuda_stream)
-            # the status words follow the batch to pinned memory; they are read when this staging slot comes round again
-            words = torch.empty(len(jp_keys), dtype=torch.int32).pin_memory()
-            words.copy_(dev[st_at:st_at + 4 * len(jp_keys)].view(torch.int32), non_blocking=True)
-            self._status[slot] = [(words, [images[k[1]] for k in jp_keys], jpeg)]
-            self._upload_done(slot, stream)
-        if pg_keys:
-            png.launch(base + gp_at, gpool.size, base + gd_at, gdesc, base, nbytes, base + gws_at, gws_bytes, base + gst_at,
-                       stream.cuda_stream, ginf)
-            words = torch.empty(len(pg_keys), dtype=torch.int32).pin_memory()
-            words.copy_(dev[gst_at:gst_at + 4 * len(pg_keys)].view(torch.int32), non_blocking=True)
-            self._status[slot] = (self._status[slot] or []) + [(words, [images[k[1]] for k in pg_keys], png)]
-            self._upload_done(slot, stream)
-        if pj_keys:
-            jpeg.launch_progressive(pj, base + pj_at[5], base + pj_at[0], base + pj_at[1], base + pj_at[2], base + pj_at[3],
-                                    base + pj_at[4], base, nbytes, base + pws_at, pws_bytes, base + pst_at, stream.cuda_stream)
-            words = torch.empty(len(pj_keys), dtype=torch.int32).pin_memory()
-            words.copy_(dev[pst_at:pst_at + 4 * len(pj_keys)].view(torch.int32), non_blocking=True)
-            self._status[slot] = (self._status[slot] or []) + [(words, [images[k[1]] for k in pj_keys], jpeg)]
-            self._upload_done(slot, stream)
-        if dec_keys:
-            rc = _lib.lib().io_rle_decode_u8(C.c_void_p(base + tab_at), C.c_size_t(ends.size), C.c_void_p(base + rd_at),
-                                             C.cast(rdesc, C.c_void_p), len(dec_keys), C.c_void_p(base),
-                                             C.c_size_t(nbytes), C.c_void_p(stream.cuda_stream))
-            _lib.check(rc, "io_rle_decode_u8")
-        if pol_keys:
-            rc = _lib.lib().io_poly_fill_u8(C.c_void_p(base + vt_at), C.c_size_t(verts.shape[0]), C.c_void_p(base + pp_at),
-                                            C.cast(pparts, C.c_void_p), n_parts, C.c_void_p(base + pm_at),
-                                            C.cast(pmasks, C.c_void_p), len(pol_keys), C.c_void_p(base), C.c_size_t(nbytes),
-                                            C.c_void_p(base + ws_at), C.c_size_t(ws_bytes), C.c_void_p(stream.cuda_stream))
-            _lib.check(rc, "io_poly_fill_u8")
-        return self._launch(base, nbytes, base + pd_at, desc, load_rgb, stream)
+        base, pending = dev.data_ptr(), []
+        for k in (2, 3, 4, 0, 1):                                    # the order of the launches on the stream
+            g = groups[k]
+            if not len(g):
+                continue
+            g.launch([base + a for a in ats[k]], base, nbytes, base + ws_at[k], ws_bytes[k], base + st_at[k],
+                     stream.cuda_stream)
+            if g.n_status:
+                # the status words follow the batch to pinned memory; they are read when this staging slot comes round again
+                words = torch.empty(g.n_status, dtype=torch.int32).pin_memory()
+                words.copy_(dev[st_at[k]:st_at[k] + 4 * g.n_status].view(torch.int32), non_blocking=True)
+                pending.append((words, g))
+        self._status[slot] = pending or None
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._events[slot] = ev
+        return self._planes(base, nbytes, base + pd_at, desc, load_rgb, stream)
 
 
 # ---- item logic of the datasets ----------------------------------------------------------------------------------------

@@ -42,7 +42,7 @@ import struct
 
 import numpy as np
 
-from . import _lib
+from . import _lib, arena
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7,
                    14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39,
@@ -1203,19 +1203,6 @@ def workspace_bytes_progressive(p):
     return b
 
 
-def launch_progressive(p, pool, tables_dev, huff_dev, desc_dev, image_dev, scan_dev, out, out_bytes, ws, ws_bytes, status,
-                       stream, concurrent=None):
-    """one ``io_jpeg_decode_prog_u8`` call for the tables ``p`` of ``descriptors_progressive``; device addresses as ints"""
-    concurrent = _PROGRESSIVE["concurrent"] if concurrent is None else int(concurrent)
-    rc = _lib.lib().io_jpeg_decode_prog_u8(
-        C.c_void_p(pool), C.c_size_t(p["pool"].size), C.c_void_p(tables_dev), p["tables"].ctypes.data_as(C.c_void_p),
-        C.c_size_t(p["tables"].size), C.c_void_p(huff_dev), p["huff"].ctypes.data_as(C.c_void_p), p["huff"].size // 272,
-        C.c_void_p(desc_dev), C.cast(p["desc"], C.c_void_p), C.c_void_p(image_dev), C.cast(p["image"], C.c_void_p),
-        len(p["desc"]), C.c_void_p(scan_dev), C.cast(p["scan"], C.c_void_p), p["n_scans"], C.c_void_p(out),
-        C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status), concurrent, C.c_void_p(stream))
-    _lib.check(rc, "io_jpeg_decode_prog_u8")
-
-
 def progressive_blobs(p):
     """the uint8 arrays of ``p`` that travel to the device, in the order (tables, huff, desc, image, scan, pool)"""
     return [p["tables"], p["huff"], np.frombuffer(p["desc"], dtype=np.uint8), np.frombuffer(p["image"], dtype=np.uint8),
@@ -1298,21 +1285,53 @@ def workspace_bytes(desc, entropy=None):
     return b
 
 
-def launch(entropy, pool, pool_bytes, tables_dev, tables, desc_dev, desc, out, out_bytes, ws, ws_bytes, status, stream,
-           info=None):
-    """one ``io_jpeg_decode_u8`` / ``io_jpeg_decode_par_u8`` call, as ``entropy`` (a ``get_entropy`` dict) says.  Device
-    addresses as ints; ``tables``: the host uint8 array, ``desc``: the host JpegDesc array, ``info``: n int32 or None."""
-    head = (C.c_void_p(pool), C.c_size_t(pool_bytes), C.c_void_p(tables_dev), tables.ctypes.data_as(C.c_void_p),
-            C.c_size_t(tables.size), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p), len(desc), C.c_void_p(out),
-            C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status))
-    if entropy["mode"] == "parallel":
-        fn = "io_jpeg_decode_par_u8"
-        rc = _lib.lib().io_jpeg_decode_par_u8(*(head + (entropy["subseq_bytes"], entropy["max_rounds"],
-                                                        C.c_void_p(info) if info else None, C.c_void_p(stream))))
-    else:
-        fn = "io_jpeg_decode_u8"
-        rc = _lib.lib().io_jpeg_decode_u8(*(head + (C.c_void_p(stream),)))
-    _lib.check(rc, fn)
+def group(images, entropy=None):
+    """``arena.Group`` of the baseline files ``images``: blobs (pool, tables, JpegDesc array), one ``io_jpeg_decode_u8`` or
+    ``io_jpeg_decode_par_u8`` call as ``entropy`` (a mode, a ``get_entropy`` dict, None: the ``set_entropy`` setting) says
+    -- the same setting sizes the workspace -- and a status word per image; ``info``: the address of n int32 or None."""
+    if not images:
+        return arena.Group()
+    e = get_entropy(entropy)
+    pool, tables, desc = descriptors(images, [0] * len(images))
+
+    def launch(addrs, out, out_bytes, ws, ws_bytes, status, stream, info=None):
+        head = (C.c_void_p(addrs[0]), C.c_size_t(pool.size), C.c_void_p(addrs[1]), tables.ctypes.data_as(C.c_void_p),
+                C.c_size_t(tables.size), C.c_void_p(addrs[2]), C.cast(desc, C.c_void_p), len(desc), C.c_void_p(out),
+                C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status))
+        if e["mode"] == "parallel":
+            fn = "io_jpeg_decode_par_u8"
+            rc = _lib.lib().io_jpeg_decode_par_u8(*(head + (e["subseq_bytes"], e["max_rounds"],
+                                                            C.c_void_p(info) if info else None, C.c_void_p(stream))))
+        else:
+            fn = "io_jpeg_decode_u8"
+            rc = _lib.lib().io_jpeg_decode_u8(*(head + (C.c_void_p(stream),)))
+        _lib.check(rc, fn)
+
+    return arena.Group([pool, tables, arena.as_bytes(desc)], ("images", "images", "descriptors"), desc, launch,
+                       lambda: workspace_bytes(desc, e), images, raise_for_status)
+
+
+def group_progressive(images, concurrent=None):
+    """``arena.Group`` of the accepted progressive files ``images``: the blobs of ``progressive_blobs``, one
+    ``io_jpeg_decode_prog_u8`` call (``concurrent``: 1 or 0 instead of the ``set_progressive`` value) with a workspace, and
+    a status word per image"""
+    if not images:
+        return arena.Group()
+    concurrent = _PROGRESSIVE["concurrent"] if concurrent is None else int(concurrent)
+    p = descriptors_progressive(images, [0] * len(images))
+
+    def launch(addrs, out, out_bytes, ws, ws_bytes, status, stream, info=None):
+        tables_dev, huff_dev, desc_dev, image_dev, scan_dev, pool_dev = addrs
+        rc = _lib.lib().io_jpeg_decode_prog_u8(
+            C.c_void_p(pool_dev), C.c_size_t(p["pool"].size), C.c_void_p(tables_dev), p["tables"].ctypes.data_as(C.c_void_p),
+            C.c_size_t(p["tables"].size), C.c_void_p(huff_dev), p["huff"].ctypes.data_as(C.c_void_p), p["huff"].size // 272,
+            C.c_void_p(desc_dev), C.cast(p["desc"], C.c_void_p), C.c_void_p(image_dev), C.cast(p["image"], C.c_void_p),
+            len(p["desc"]), C.c_void_p(scan_dev), C.cast(p["scan"], C.c_void_p), p["n_scans"], C.c_void_p(out),
+            C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status), concurrent, C.c_void_p(stream))
+        _lib.check(rc, "io_jpeg_decode_prog_u8")
+
+    return arena.Group(progressive_blobs(p), ("images", "images", "descriptors", "descriptors", "descriptors", "images"),
+                       p["desc"], launch, lambda: workspace_bytes_progressive(p), images, raise_for_status)
 
 
 def raise_for_status(status, images):
@@ -1343,9 +1362,8 @@ def decode(images, device, out=None, entropy=None, info=False, concurrent=None):
             raise TypeError("jpeg.decode takes JpegImage objects (got %s)" % type(im).__name__)
         im._require()
     sizes = [im.H * im.W * 3 for im in images]
-    offs = [0]
-    for s in sizes[:-1]:
-        offs.append(offs[-1] + (s + 15) // 16 * 16)
+    lay = arena.Layout()
+    offs = [lay.add(s) for s in sizes]
     total = offs[-1] + sizes[-1]
     if out is None:
         out = torch.empty(total, dtype=torch.uint8, device=device)
@@ -1354,36 +1372,13 @@ def decode(images, device, out=None, entropy=None, info=False, concurrent=None):
     out = out.view(-1)
     base_idx = [k for k, im in enumerate(images) if not im.progressive]
     prog_idx = [k for k, im in enumerate(images) if im.progressive]
-    blobs = []
-    if base_idx:
-        pool, tables, desc = descriptors([images[k] for k in base_idx], [offs[k] for k in base_idx])
-        blobs += [tables, np.frombuffer(desc, dtype=np.uint8), pool]
-    if prog_idx:
-        prog = descriptors_progressive([images[k] for k in prog_idx], [offs[k] for k in prog_idx])
-        blobs += progressive_blobs(prog)
-    at, cursor = [], 0
-    for b in blobs:
-        at.append(cursor)
-        cursor += (b.size + 15) // 16 * 16
-    host = np.zeros(max(cursor, 16), np.uint8)
-    for a, b in zip(at, blobs):
-        host[a:a + b.size] = b
-    dev = torch.from_numpy(host).to(out.device)
+    groups = [group([images[k] for k in base_idx], setting), group_progressive([images[k] for k in prog_idx], concurrent)]
+    groups[0].set_outs(offs[k] for k in base_idx)
+    groups[1].set_outs(offs[k] for k in prog_idx)
     # one status vector: the words of the baseline images, then those of the progressive ones
     status = torch.empty(len(images), dtype=torch.int32, device=out.device)
     words = torch.zeros(len(images), dtype=torch.int32, device=out.device)
-    base = dev.data_ptr()
-    stream = torch.cuda.current_stream(out.device).cuda_stream
-    if base_idx:
-        ws = torch.empty(workspace_bytes(desc, setting), dtype=torch.uint8, device=out.device)
-        launch(setting, base + at[2], pool.size, base + at[0], tables, base + at[1], desc, out.data_ptr(), out.numel(),
-               ws.data_ptr(), ws.numel(), status.data_ptr(), stream, info=words.data_ptr() if info else None)
-    if prog_idx:
-        a = at[3:] if base_idx else at
-        pws = torch.empty(workspace_bytes_progressive(prog), dtype=torch.uint8, device=out.device)
-        launch_progressive(prog, base + a[5], base + a[0], base + a[1], base + a[2], base + a[3], base + a[4], out.data_ptr(),
-                           out.numel(), pws.data_ptr(), pws.numel(), status.data_ptr() + 4 * len(base_idx), stream,
-                           concurrent=concurrent)
+    arena.decode_into(groups, out, status, words if info else None)
     order = base_idx + prog_idx
     if prog_idx and base_idx:
         back = torch.from_numpy(np.argsort(order))

@@ -30,7 +30,7 @@ import zlib
 
 import numpy as np
 
-from . import _lib
+from . import _lib, arena
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 STATUS = {1: "block type 3", 2: "a stored block whose length and complement disagree", 3: "an invalid code-length set",
@@ -867,7 +867,7 @@ def _check_chunk_bytes(chunk_bytes, who):
 
 
 def set_inflate(mode, chunk_bytes=DEFAULT_CHUNK_BYTES):
-    """The inflate stage ``decode``, ``workspace_bytes`` / ``launch`` and with them ``PairRenderer`` and ``dense_eval`` use:
+    """The inflate stage ``decode``, ``workspace_bytes`` / ``group`` and with them ``PairRenderer`` and ``dense_eval`` use:
     "sequential" -- one wave per image (``io_png_decode``) -- or "parallel" -- one stream on many waves from found block
     starts (``io_png_decode_par``, csrc/png_inflate_par.h), chunks of ``chunk_bytes``.  Bytes and status words do not
     depend on it.  Module-wide; the default is "sequential", the environment variable IO_PNG_INFLATE=parallel selects the
@@ -906,21 +906,30 @@ def workspace_bytes(desc, inflate=None):
     return b
 
 
-def launch(pool, pool_bytes, desc_dev, desc, out, out_bytes, ws, ws_bytes, status, stream, inflate=None, info=None):
-    """one ``io_png_decode`` / ``io_png_decode_par`` call, as the setting (or ``inflate``, a mode or a ``get_inflate``
-    dict) says.  Device addresses as ints; ``desc``: the host PngDesc array; ``info``: the address of int32 info words
-    per image (parallel only) or None."""
+def group(images, inflate=None):
+    """``arena.Group`` of the PNG files ``images``: blobs (pool, PngDesc array), one ``io_png_decode`` or
+    ``io_png_decode_par`` call as ``inflate`` (a mode, a ``get_inflate`` dict, None: the ``set_inflate`` setting) says --
+    the same setting sizes the workspace -- and a status word per image; ``info``: the address of int32 info words per
+    image (parallel only) or None."""
+    if not images:
+        return arena.Group()
     s = get_inflate(inflate)
-    head = (C.c_void_p(pool), C.c_size_t(pool_bytes), C.c_void_p(desc_dev), C.cast(desc, C.c_void_p), len(desc),
-            C.c_void_p(out), C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status))
-    if s["mode"] == "parallel":
-        rc = _lib.lib().io_png_decode_par(*(head + (s["chunk_bytes"], C.c_void_p(info), C.c_void_p(stream))))
-        _lib.check(rc, "io_png_decode_par")
-    else:
-        if info is not None:
-            raise ValueError("png.launch: info words exist with the parallel inflate stage only")
-        rc = _lib.lib().io_png_decode(*(head + (C.c_void_p(stream),)))
-        _lib.check(rc, "io_png_decode")
+    pool, desc = descriptors(images, [0] * len(images))
+
+    def launch(addrs, out, out_bytes, ws, ws_bytes, status, stream, info=None):
+        head = (C.c_void_p(addrs[0]), C.c_size_t(pool.size), C.c_void_p(addrs[1]), C.cast(desc, C.c_void_p), len(desc),
+                C.c_void_p(out), C.c_size_t(out_bytes), C.c_void_p(ws), C.c_size_t(ws_bytes), C.c_void_p(status))
+        if s["mode"] == "parallel":
+            rc = _lib.lib().io_png_decode_par(*(head + (s["chunk_bytes"], C.c_void_p(info), C.c_void_p(stream))))
+            _lib.check(rc, "io_png_decode_par")
+        else:
+            if info is not None:
+                raise ValueError("png.group: info words exist with the parallel inflate stage only")
+            rc = _lib.lib().io_png_decode(*(head + (C.c_void_p(stream),)))
+            _lib.check(rc, "io_png_decode")
+
+    return arena.Group([pool, arena.as_bytes(desc)], ("images", "descriptors"), desc, launch,
+                       lambda: workspace_bytes(desc, s), images, raise_for_status)
 
 
 def raise_for_status(status, images):
@@ -956,30 +965,19 @@ def decode(images, device, out=None, check=True, inflate=None, info=False):
             raise TypeError("png.decode takes PngImage objects (got %s)" % type(im).__name__)
         im._require()
     sizes = [im.out_bytes for im in images]
-    offs = [0]
-    for s in sizes[:-1]:
-        offs.append(offs[-1] + (s + 15) // 16 * 16)
+    lay = arena.Layout()
+    offs = [lay.add(s) for s in sizes]
     total = offs[-1] + sizes[-1]
     if out is None:
         out = torch.empty(total, dtype=torch.uint8, device=device)
     elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < total:
         raise ValueError("png.decode: out must be a contiguous uint8 device tensor of at least %d bytes" % total)
     out = out.view(-1)
-    pool, desc = descriptors(images, offs)
-    dbytes = C.sizeof(desc)
-    host = np.zeros(dbytes + max(pool.size, 16), np.uint8)
-    host[:dbytes] = np.frombuffer(desc, dtype=np.uint8)
-    host[dbytes:dbytes + pool.size] = pool
-    dev = torch.from_numpy(host).to(out.device)
-    ws = torch.empty(workspace_bytes(desc, setting), dtype=torch.uint8, device=out.device)
+    g = group(images, setting)
+    g.set_outs(offs)
     status = torch.empty(len(images), dtype=torch.int32, device=out.device)
     words = torch.empty(len(images), dtype=torch.int32, device=out.device) if info else None
-    base = dev.data_ptr()
-    launch(base + dbytes, pool.size, base, desc, out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel(),
-           status.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream, setting,
-           words.data_ptr() if info else None)
-    ws.record_stream(torch.cuda.current_stream(out.device))
-    dev.record_stream(torch.cuda.current_stream(out.device))
+    arena.decode_into([g], out, status, words)
     res = []
     for o, s, im in zip(offs, sizes, images):
         t = out[o:o + s]

@@ -26,7 +26,7 @@ import numbers
 
 import numpy as np
 
-from . import _lib
+from . import _lib, arena
 from . import rle as _rle
 from .rle import EncodedMasks, RLEMasks
 
@@ -273,46 +273,35 @@ def workspace_bytes(parts, n_parts, masks):
     return b
 
 
+def group(refs):
+    """``arena.Group`` of the polygon instances ``refs`` (the ``tables`` of ``descriptors``): blobs (vertices, PolyPart
+    array, PolyMask array), one ``io_poly_fill_u8`` call with a workspace, no status words"""
+    if not refs:
+        return arena.Group()
+    verts, parts, masks, n_parts = descriptors(refs, [0] * len(refs))
+
+    def launch(addrs, out, out_bytes, ws, ws_bytes, status, stream, info=None):
+        rc = _lib.lib().io_poly_fill_u8(C.c_void_p(addrs[0]), C.c_size_t(verts.shape[0]), C.c_void_p(addrs[1]),
+                                        C.cast(parts, C.c_void_p), n_parts, C.c_void_p(addrs[2]), C.cast(masks, C.c_void_p),
+                                        len(masks), C.c_void_p(out), C.c_size_t(out_bytes), C.c_void_p(ws),
+                                        C.c_size_t(ws_bytes), C.c_void_p(stream))
+        _lib.check(rc, "io_poly_fill_u8")
+
+    return arena.Group([arena.as_bytes(verts), arena.as_bytes(parts), arena.as_bytes(masks)],
+                       ("masks", "descriptors", "descriptors"), masks, launch,
+                       lambda: workspace_bytes(parts, n_parts, masks))
+
+
 def decode(poly_masks, device, out=None):
     """uint8 device tensor [n, H, W] of the masks: the polygon instances through ``io_poly_fill_u8``, the run-length ones
     through ``io_rle_decode_u8`` (both enqueued on the current stream)."""
-    import torch
     _lib.require_gpu()
-    device = torch.device(device)
     n, H, W = poly_masks.shape
-    if out is None:
-        out = torch.empty((n, H, W), dtype=torch.uint8, device=device)
-    elif tuple(out.shape) != (n, H, W) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("poly.decode: out must be a contiguous uint8 device tensor of shape %s" % ((n, H, W),))
-    if n == 0:
-        return out
+    out = _rle.device_out("poly.decode", (n, H, W), device, out)
     pol = [i for i in range(n) if poly_masks.is_polygon(i)]
     enc = [i for i in range(n) if not poly_masks.is_polygon(i)]
-    verts, parts, masks, n_parts = descriptors([(poly_masks, i) for i in pol], [i * H * W for i in pol])
-    ends, rdesc = _rle.descriptors([poly_masks.rle_ref(i) for i in enc], [i * H * W for i in enc])
-    blobs = [verts.view(np.uint8).reshape(-1), np.frombuffer(parts, dtype=np.uint8), np.frombuffer(masks, dtype=np.uint8),
-             ends.view(np.uint8), np.frombuffer(rdesc, dtype=np.uint8)]
-    at, cursor = [], 0
-    for b in blobs:                                            # the tables hold int64: keep them aligned
-        at.append(cursor)
-        cursor += (b.size + 15) // 16 * 16
-    host = np.zeros(max(cursor, 16), np.uint8)
-    for a, b in zip(at, blobs):
-        host[a:a + b.size] = b
-    dev = torch.from_numpy(host).to(out.device)
-    base = dev.data_ptr()
-    stream = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-    L = _lib.lib()
-    if pol:
-        ws = torch.empty(workspace_bytes(parts, n_parts, masks), dtype=torch.uint8, device=out.device)
-        rc = L.io_poly_fill_u8(C.c_void_p(base + at[0]), C.c_size_t(verts.shape[0]), C.c_void_p(base + at[1]),
-                               C.cast(parts, C.c_void_p), n_parts, C.c_void_p(base + at[2]), C.cast(masks, C.c_void_p),
-                               len(pol), C.c_void_p(out.data_ptr()), C.c_size_t(n * H * W), C.c_void_p(ws.data_ptr()),
-                               C.c_size_t(ws.numel()), stream)
-        _lib.check(rc, "io_poly_fill_u8")
-    if enc:
-        rc = L.io_rle_decode_u8(C.c_void_p(base + at[3]), C.c_size_t(ends.size), C.c_void_p(base + at[4]),
-                                C.cast(rdesc, C.c_void_p), len(enc), C.c_void_p(out.data_ptr()), C.c_size_t(n * H * W),
-                                stream)
-        _lib.check(rc, "io_rle_decode_u8")
+    groups = [group([(poly_masks, i) for i in pol]), _rle.group([poly_masks.rle_ref(i) for i in enc])]
+    groups[0].set_outs(i * H * W for i in pol)
+    groups[1].set_outs(i * H * W for i in enc)
+    arena.decode_into(groups, out)
     return out

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, arena
 
 
 def _counts_from_string(s):
@@ -269,28 +269,38 @@ def descriptors(tables, out_offs):
     return (np.concatenate(parts) if parts else np.zeros(0, np.uint32)), desc
 
 
+def group(refs):
+    """``arena.Group`` of the run-length instances ``refs`` (the ``tables`` of ``descriptors``): blobs (ends, RleDesc
+    array), one ``io_rle_decode_u8`` call, no workspace and no status words"""
+    if not refs:
+        return arena.Group()
+    ends, desc = descriptors(refs, [0] * len(refs))
+
+    def launch(addrs, out, out_bytes, ws, ws_bytes, status, stream, info=None):
+        rc = _lib.lib().io_rle_decode_u8(C.c_void_p(addrs[0]), C.c_size_t(ends.size), C.c_void_p(addrs[1]),
+                                         C.cast(desc, C.c_void_p), len(desc), C.c_void_p(out), C.c_size_t(out_bytes),
+                                         C.c_void_p(stream))
+        _lib.check(rc, "io_rle_decode_u8")
+
+    return arena.Group([arena.as_bytes(ends), arena.as_bytes(desc)], ("masks", "descriptors"), desc, launch)
+
+
+def device_out(who, shape, device, out):
+    """the uint8 [n, H, W] device tensor ``rle.decode`` / ``poly.decode`` fill: ``out`` checked, or a new one"""
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=torch.device(device))
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous uint8 device tensor of shape %s" % (who, tuple(shape)))
+    return out
+
+
 def decode(rle_masks, device, out=None):
     """uint8 device tensor [n, H, W] of the masks, through ``io_rle_decode_u8`` (enqueued on the current stream)."""
-    import torch
     _lib.require_gpu()
-    device = torch.device(device)
     n, H, W = rle_masks.shape
-    if out is None:
-        out = torch.empty((n, H, W), dtype=torch.uint8, device=device)
-    elif tuple(out.shape) != (n, H, W) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("rle.decode: out must be a contiguous uint8 device tensor of shape %s" % ((n, H, W),))
-    if n == 0:
-        return out
-    ends, desc = descriptors([(rle_masks, i) for i in range(n)], [i * H * W for i in range(n)])
-    dbytes = C.sizeof(desc)
-    tbytes = (ends.nbytes + 15) // 16 * 16                 # the descriptors hold int64: keep them aligned
-    host = np.empty(tbytes + dbytes, np.uint8)
-    host[:ends.nbytes] = ends.view(np.uint8)
-    host[tbytes:] = np.frombuffer(desc, dtype=np.uint8)
-    dev = torch.from_numpy(host).to(out.device)
-    rc = _lib.lib().io_rle_decode_u8(C.c_void_p(dev.data_ptr()), C.c_size_t(ends.size),
-                                     C.c_void_p(dev.data_ptr() + tbytes), C.cast(desc, C.c_void_p), n,
-                                     C.c_void_p(out.data_ptr()), C.c_size_t(n * H * W),
-                                     C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream))
-    _lib.check(rc, "io_rle_decode_u8")
+    out = device_out("rle.decode", (n, H, W), device, out)
+    g = group([(rle_masks, i) for i in range(n)])
+    g.set_outs(range(0, n * H * W, H * W))
+    arena.decode_into([g], out)
     return out

@@ -317,3 +317,115 @@ def test_eval_dense_depth_png_device_equals_host(tmp_path):
     assert np.abs(rows["rgb host"]).max() > 0 and np.array_equal(rows["rgb host"], rows["rgb device"])
     with pytest.raises(ValueError, match="'host' or 'device'"):
         dense_eval.KITTIEigenReader(lst, str(tmp_path), png="gpu")
+
+
+# ---- every region of the renderer's arena at once ------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def everything():
+    """Four images -- an array, a baseline JPEG file, a progressive one, a PNG file -- with dense masks, ``RLEMasks``,
+    ``PolyMasks`` that hold polygons and a run-length instance, and dense masks again: every codec group of
+    ``PairRenderer.render`` has members, beside uploaded arrays.  (arrays, dense masks, items, the planes of the batch as
+    arrays and dense masks, make): ``make()`` builds the encoded batch under the settings of its moment."""
+    import jpeg_prog_cases
+    from instaorder_amd import jpeg, poly, rle
+    base, prog = jpeg_cases.load()[1], jpeg_prog_cases.load()[1]
+    names = ["21x35_444_q85", "40x24_422_q85", "33x47_420_q85", "33x47_420_lumafirst"]
+    arrays = [base[names[0]][1], base[names[1]][1], prog[names[2]][1], prog[names[3]][1]]
+    dense, items = [], []
+    for ii, a in enumerate(arrays):
+        H, W = a.shape[:2]
+        y, x = np.mgrid[0:H, 0:W]
+        dense.append(np.stack([(x > W // 4) & (y < 2 * H // 3), (x - W / 2) ** 2 + (y - H / 2) ** 2 < (min(H, W) / 3) ** 2,
+                               (x + y) % 7 < 3]).astype(np.uint8))
+        hw = max(H, W)
+        items.append((ii, 0, 1, (W // 4 - 6, H // 4 - 5, 27, 27), datasets.INTER_CUBIC, bool(ii % 2)))
+        items.append((ii, 1, 2, (-((hw - W) // 2), -((hw - H) // 2), hw, hw), datasets.INTER_LINEAR, not ii % 2))
+        items.append((ii, 2, 0, (0, 0, W, H), datasets.INTER_LINEAR, False))
+    H2, W2 = arrays[2].shape[:2]
+    crowd = rle.RLEMasks.from_dense(dense[2][1:2]).counts[0]
+    pm = poly.PolyMasks([[[2.5, 3.0, W2 - 3.0, 4.5, W2 / 2, H2 - 2.0]], {"size": [H2, W2], "counts": [int(c) for c in crowd]},
+                         [[-4, -3, W2 + 2, H2 / 2, 3, H2 + 5], [1, 1, 5, 1, 5, 5]]], H2, W2, values=[1, 1, 9])
+    assert pm.is_polygon(0) and not pm.is_polygon(1) and pm.is_polygon(2)
+    dense[2] = pm.to_dense()
+    assert all(m[i].any() for m in dense for i in range(3))
+
+    def make():
+        assert jpeg.get_progressive() == "device"
+        images = [arrays[0], jpeg_cases.image(names[1]), jpeg.JpegImage(prog[names[2]][0], name=names[2]),
+                  _as_png(arrays[3], "image3.png")]
+        assert images[2].progressive and images[2].supported and not images[1].progressive
+        return images, [dense[0], rle.RLEMasks.from_dense(dense[1] != 0), pm, dense[3]]
+
+    want = [t.cpu().numpy() for t in datasets.PairRenderer(64, MEAN, STD).render(arrays, dense, items)]
+    assert np.abs(want[0]).max() > 0 and want[1].any() and want[2].any()
+    return arrays, dense, items, want, make
+
+
+@pytest.fixture
+def device_progressive():
+    from instaorder_amd import jpeg
+    was = dict(jpeg._PROGRESSIVE)
+    jpeg.set_progressive("device")
+    yield
+    jpeg.set_progressive(was["mode"], was["concurrent"])
+
+
+@pytest.mark.parametrize("stages", ["sequential", "parallel"])
+def test_renderer_with_every_region_non_empty_equals_arrays(everything, device_progressive, stages):
+    """all five codec groups, uploaded arrays and dense masks in one batch, under both entropy and both inflate stages:
+    the three planes are those of the batch as arrays and dense masks, bit for bit"""
+    from instaorder_amd import jpeg
+    arrays, dense, items, want, make = everything
+    was_e, was_i = jpeg.get_entropy(), png.get_inflate()
+    try:
+        jpeg.set_entropy(stages, was_e["subseq_bytes"], was_e["max_rounds"])
+        png.set_inflate(stages, was_i["chunk_bytes"])
+        images, masks = make()
+        r = datasets.PairRenderer(64, MEAN, STD)
+        for turn in range(3):                                    # both staging slots, and the first one again
+            got = r.render(images, masks, items)
+            for g, w, plane in zip(got, want, ("rgb", "modal1", "modal2")):
+                assert np.array_equal(g.cpu().numpy(), w), (stages, turn, plane)
+        r.check_status()
+    finally:
+        jpeg.set_entropy(was_e["mode"], was_e["subseq_bytes"], was_e["max_rounds"])
+        png.set_inflate(was_i["mode"], was_i["chunk_bytes"])
+    up = r.last_upload
+    assert up["images"] > arrays[0].size and up["masks"] > dense[0].size + dense[3].size
+    assert up["total"] >= up["images"] + up["masks"] + up["descriptors"]
+
+
+def test_renderer_with_empty_image_regions(everything, device_progressive):
+    """the same batch without its images: no image is uploaded or decoded, the masks are the same and rgb is zero"""
+    arrays, dense, items, want, make = everything
+    images, masks = make()
+    r = datasets.PairRenderer(64, MEAN, STD)
+    for ims in (images, [None] * len(images)):
+        rgb, m1, m2 = r.render(ims, masks, items, load_rgb=False)
+        assert r.last_upload["images"] == 0
+        assert tuple(rgb.shape) == want[0].shape and float(rgb.abs().max()) == 0.0
+        assert np.array_equal(m1.cpu().numpy(), want[1]) and np.array_equal(m2.cpu().numpy(), want[2])
+    r.check_status()
+
+
+def test_renderer_reports_a_failure_of_one_codec_beside_healthy_ones(everything, device_progressive):
+    """a truncated PNG stream in one batch, a truncated baseline scan in the next, both beside the healthy members of the
+    other groups: the first is named when its staging slot comes round, the second by check_status(); a rejected stream
+    is a status word, and the renderer goes on"""
+    arrays, dense, items, want, make = everything
+    images, masks = make()
+    bad_png = images[3].with_stream(images[3].deflate_bytes()[:40], name="truncated.png")
+    bad_jpg = images[1].with_entropy(images[1].entropy_bytes()[:40], "truncated.jpg")
+    r = datasets.PairRenderer(64, MEAN, STD)
+    r.render(images[:3] + [bad_png], masks, items)
+    r.render([images[0], bad_jpg] + images[2:], masks, items)
+    with pytest.raises(RuntimeError, match="PNG decode failed: truncated.png") as e:
+        r.render(images, masks, items)
+    assert "truncated.jpg" not in str(e.value)
+    with pytest.raises(RuntimeError, match="JPEG decode failed: truncated.jpg") as e:
+        r.check_status()
+    assert "truncated.png" not in str(e.value)
+    got = r.render(images, masks, items)
+    for g, w, plane in zip(got, want, ("rgb", "modal1", "modal2")):
+        assert np.array_equal(g.cpu().numpy(), w), plane
+    r.check_status()
