@@ -972,6 +972,27 @@ int io_unet_head(const float* act, const float* wo, const float* bo, const float
                  int P, int HW, int Cs, float th, uint8_t* comp, int32_t* counts, float* logits, float* partials,
                  size_t partial_floats, float* loss_sums, hipStream_t stream);
 
+/* ---- PCNet-M training: the backward of the three UNet-only operators (csrc/unet.hip; instaorder_amd/ops.py).  Vector stores,
+ * no floating-point atomics, every sum in a fixed order: two runs give the same bits.
+ *
+ * io_maxpool2x2_bwd: dx[N][H][W][C] from dy[N][H/2][W/2][C] and the pooled tensor x: the gradient goes to the first maximum of
+ * each 2x2 window in (row, column) order (PyTorch's tie rule), 0 to the other three; add (NULL, or shaped like dx; may BE
+ * dx) is summed in.  H and W even, C % 4 == 0. */
+int io_maxpool2x2_bwd(const float* dy, const float* x, const float* add, int N, int H, int W, int C, float* dx,
+                      hipStream_t stream);
+/* Backward of io_up2x_concat_fwd from dcat[N][2h][2w][C2 + C1]: dx2[N][2h][2w][C2] = its first C2 channels; dx1[N][h][w][C1] =
+ * the transpose of the interpolation in gather form (each source pixel sums, in (row, column) order and with the forward's
+ * weights, what the destination pixels that read it contribute).  h == 1 or w == 1 is fine; C1 % 4 == C2 % 4 == 0. */
+int io_up2x_concat_bwd(const float* dcat, int N, int h, int w, int C2, int C1, float* dx2, float* dx1, hipStream_t stream);
+/* Backward of the head under MaskWeightedCrossEntropyLoss, on act[P][HW][Cs] (Cs == 64, the training layout):
+ * dlogit_c = wgt (softmax(l)_c - [c == target]) scale (* gscale[0] when gscale, a device scalar, is given), wgt = inmask_weight
+ * where eraser != 0, else 1; dx[P][HW][Cs] = dlogit . wo, dwo[2][Cs], dbo[2], and (when not NULL) loss_sums[2] as io_unet_head's
+ * loss mode defines them.  The logits are not written.  partials: io_unet_head_bwd_partial_floats(P, HW) floats. */
+size_t io_unet_head_bwd_partial_floats(int P, int HW);
+int io_unet_head_bwd(const float* act, const float* wo, const float* bo, const uint8_t* target, const float* eraser, int P,
+                     int HW, int Cs, float inmask_weight, float scale, const float* gscale, float* dx, float* dwo, float* dbo,
+                     float* loss_sums, float* partials, size_t partial_floats, hipStream_t stream);
+
 /* ---- measurement aid (bench.py): HIP-event timing of every launch, per kernel class, on the launch
  * stream.  Process-global; io_prof_end synchronises on the recorded events and returns the number of
  * classes written.  flops / bytes are the ALGORITHMIC figures of the timed launches (the direct convolution's count). */

@@ -299,6 +299,13 @@ SIGNATURES = {
     "io_unet_head_partial_floats": (_Z, [_I, _I]),
     # act, wo, bo, m1, m2, target, P, HW, Cs, th, comp, counts, logits, partials, partial_floats, loss_sums, stream
     "io_unet_head": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _Z, _P, _P]),
+    # dy, x, add, N, H, W, C, dx, stream
+    "io_maxpool2x2_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    # dcat, N, h, w, C2, C1, dx2, dx1, stream
+    "io_up2x_concat_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "io_unet_head_bwd_partial_floats": (_Z, [_I, _I]),
+    # act, wo, bo, target, eraser, P, HW, Cs, inmask_weight, scale, gscale, dx, dwo, dbo, loss_sums, partials, partial_floats, stream
+    "io_unet_head_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "io_prof_begin": (_I, []),
     "io_prof_begin_ex": (_I, [_I]),
     "io_prof_end": (_I, [C.POINTER(ProfEntry), _I]),

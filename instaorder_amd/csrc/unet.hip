@@ -1,5 +1,8 @@
-// PCNet-M (UNet) inference kernels, NHWC fp32: what the eval-mode forward of instaorder_amd/unet.py needs beyond the dense
-// convolution launcher (io_conv2d_fwd_bias_dt: Co % 64 == 0, Ci % 32 == 0):
+// PCNet-M (UNet) kernels, NHWC fp32.  Training adds the backward of the three UNet-only operators (the convolutions and
+// BatchNorms of a training step are the dense launchers'): io_maxpool2x2_bwd, io_up2x_concat_bwd, io_unet_head_bwd -- one pass
+// over each tensor in 16-byte accesses, no floating-point atomics, every sum in a fixed order.  Inference: what the
+// eval-mode forward of instaorder_amd/unet.py needs beyond the dense convolution launcher (io_conv2d_fwd_bias_dt:
+// Co % 64 == 0, Ci % 32 == 0):
 //   io_conv3x3_co32_fwd  3x3 / stride 1 / pad 1 convolution with 32 output channels, + bias (+ ReLU)
 //   io_maxpool2x2_fwd    nn.MaxPool2d(2)
 //   io_up2x_concat_fwd   cat([x2, bilinear x2 (align_corners) of x1], channel) in one pass
@@ -284,6 +287,213 @@ __global__ __launch_bounds__(kThreads) void unet_loss_reduce_kernel(const float*
     if (threadIdx.x < 2) sums[threadIdx.x] = (float)red[threadIdx.x][0];
 }
 
+// ---- training: the backward of the three UNet-only operators -------------------------------------------------------------
+// Backward of nn.MaxPool2d(2): a thread owns 4 channels of one 2x2 window.  The gradient goes to the FIRST maximum in (row,
+// column) order (PyTorch's rule: a later element replaces the running maximum only when strictly greater), the other three
+// positions get 0; ``add`` (shaped like dx, may BE dx: every element is read by the thread that then writes it) is summed in.
+__global__ __launch_bounds__(kThreads) void maxpool2x2_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                  const float* add, int H, int W, int C4, size_t total,
+                                                                  float* dx) {
+    const int OW = W / 2, OH = H / 2;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (size_t)gridDim.x * kThreads) {
+        const int q = (int)(i % C4);
+        size_t p = i / C4;
+        const int ow = (int)(p % OW);
+        p /= OW;
+        const int oh = (int)(p % OH);
+        const size_t n = p / OH;
+        const size_t o00 = (((n * H + 2 * oh) * W + 2 * ow) * C4 + q) * 4;
+        const size_t off[4] = {o00, o00 + (size_t)C4 * 4, o00 + (size_t)W * C4 * 4, o00 + ((size_t)W + 1) * C4 * 4};
+        const f32x4 g = io_ldv(dy + i * 4);
+        f32x4 v[4], r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = io_ldv(x + off[k]);
+            r[k] = add ? io_ldv(add + off[k]) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float m = v[0][e];
+            int at = 0;
+#pragma unroll
+            for (int k = 1; k < 4; ++k)
+                if (v[k][e] > m) {
+                    m = v[k][e];
+                    at = k;
+                }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k][e] += (at == k) ? g[e] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) io_stv(dx + off[k], r[k]);
+    }
+}
+
+// dx2 = the first C2 channels of dcat: a thread moves 4 channels of one pixel
+__global__ __launch_bounds__(kThreads) void concat_split_kernel(const float* __restrict__ dcat, int C2q, int Cq, size_t total,
+                                                                float* __restrict__ dx2) {
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (size_t)gridDim.x * kThreads) {
+        const size_t pix = i / C2q;
+        const int q = (int)(i - pix * C2q);
+        io_stv(dx2 + i * 4, io_ldv(dcat + (pix * Cq + q) * 4));
+    }
+}
+
+// The weight with which destination index ``dst`` of the x2 interpolation reads source index ``src`` (0: it does not): the
+// forward's own lerp_aligned, so the transpose uses the weights the forward used.  A destination at the clamped edge reads
+// one source twice (i0 == i1): both weights count.
+__device__ __forceinline__ float lerp_weight_of(int dst, int h, int src) {
+    const Lerp l = lerp_aligned(dst, h);
+    return (l.i0 == src ? l.w0 : 0.f) + (l.i1 == src ? l.w1 : 0.f);
+}
+
+// dx1 = transpose of the interpolation, in gather form: a thread owns 4 channels of one SOURCE pixel and sums, in (row,
+// column) order, what the destination pixels that read it contribute.  A source index s is read by destinations within
+// [2 s - 2, 2 s + 2] (the scale (h - 1) / (2 h - 1) lies in [1/3, 1/2)); the window below has one more on the right for the
+// rounding of the forward's fp32 index, and a destination outside the support simply has weight 0.
+constexpr int kUpWin = 6;
+__global__ __launch_bounds__(kThreads) void up2x_bwd_kernel(const float* __restrict__ dcat, int h, int w, int C2q, int C1q,
+                                                            size_t total, float* __restrict__ dx1) {
+    const int Cq = C2q + C1q, OH = 2 * h, OW = 2 * w;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (size_t)gridDim.x * kThreads) {
+        const int q = (int)(i % C1q);
+        size_t p = i / C1q;
+        const int sx = (int)(p % w);
+        p /= w;
+        const int sy = (int)(p % h);
+        const size_t n = p / h;
+        float wy[kUpWin], wx[kUpWin];
+#pragma unroll
+        for (int k = 0; k < kUpWin; ++k) {
+            const int oy = 2 * sy - 2 + k, ox = 2 * sx - 2 + k;
+            wy[k] = (oy >= 0 && oy < OH) ? lerp_weight_of(oy, h, sy) : 0.f;
+            wx[k] = (ox >= 0 && ox < OW) ? lerp_weight_of(ox, w, sx) : 0.f;
+        }
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ky = 0; ky < kUpWin; ++ky) {
+            if (wy[ky] == 0.f) continue;
+            const float* row = dcat + ((n * OH + (size_t)(2 * sy - 2 + ky)) * OW * Cq + C2q + q) * 4;
+#pragma unroll
+            for (int kx = 0; kx < kUpWin; ++kx) {
+                if (wx[kx] == 0.f) continue;
+                acc += (wy[ky] * wx[kx]) * io_ldv(row + (size_t)(2 * sx - 2 + kx) * Cq * 4);
+            }
+        }
+        io_stv(dx1 + i * 4, acc);
+    }
+}
+
+// Backward of the 1x1 head under MaskWeightedCrossEntropyLoss, one pass over the last activation x[pixels][64].  A block owns
+// 256 consecutive pixels; 16 neighbouring lanes own one pixel (lane q of the group: channels 4 q .. 4 q + 3), so every load of x
+// and every store of dx is a contiguous 256-byte row.  Per pixel: the two logits (16-lane butterfly: every lane ends with
+// the same bits), dlogit_c = wgt (softmax_c - [c == target]) scale, dx = dlogit . wo, and the lane's share of dwo; lane 0 of
+// the group also keeps dbo and the pixel's cross-entropy term.  Block partials [128 dwo | 2 dbo | 2 CE sums] are written in
+// block order and added by unet_head_bwd_reduce_kernel in a fixed order: no atomics, two runs give the same bits.
+constexpr int kHeadCs = 64, kHeadCols = 2 * kHeadCs + 4;
+__global__ __launch_bounds__(kThreads) void unet_head_bwd_kernel(const float* __restrict__ x, const float* __restrict__ wo,
+                                                                 const float* __restrict__ bo, const uint8_t* __restrict__ target,
+                                                                 const float* __restrict__ eraser, size_t total,
+                                                                 float inmask_weight, float scale, const float* __restrict__ gscale,
+                                                                 float* __restrict__ dx, float* __restrict__ partials) {
+    __shared__ float red[kThreads / 64][kHeadCols];
+    const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const f32x4 w0 = io_ldv(wo + 4 * q), w1 = io_ldv(wo + kHeadCs + 4 * q);
+    const float b0 = bo[0], b1 = bo[1];
+    const float sc = gscale ? scale * gscale[0] : scale;
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+    float s4[4] = {0.f, 0.f, 0.f, 0.f};                 // dbo[0], dbo[1], CE inside, CE outside (lane 0 of a group only)
+    const size_t base = (size_t)blockIdx.x * kThreads;
+#pragma unroll 4
+    for (int it = 0; it < 16; ++it) {
+        const size_t pix = base + it * 16 + g;
+        const bool on = pix < total;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (on) v = io_ldv(x + pix * kHeadCs + 4 * q);
+        float l0 = 0.f, l1 = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            l0 = fmaf(v[e], w0[e], l0);
+            l1 = fmaf(v[e], w1[e], l1);
+        }
+#pragma unroll
+        for (int s = 8; s >= 1; s >>= 1) {
+            l0 += __shfl_xor(l0, s);
+            l1 += __shfl_xor(l1, s);
+        }
+        if (on) {
+            l0 += b0;
+            l1 += b1;
+            const float er = eraser[pix];
+            const bool t1 = target[pix] != 0;
+            const float mx = fmaxf(l0, l1);
+            const float e0 = expf(l0 - mx), e1 = expf(l1 - mx), se = e0 + e1;
+            const float wgt = (er != 0.f ? inmask_weight : 1.f) * sc;
+            const float d0 = wgt * (e0 / se - (t1 ? 0.f : 1.f)), d1 = wgt * (e1 / se - (t1 ? 1.f : 0.f));
+            io_stv(dx + pix * kHeadCs + 4 * q, d0 * w0 + d1 * w1);
+            a0 += d0 * v;
+            a1 += d1 * v;
+            if (q == 0) {
+                const float ce = mx + logf(se) - (t1 ? l1 : l0);
+                s4[0] += d0;
+                s4[1] += d1;
+                if (er != 0.f) s4[2] += ce; else s4[3] += ce;
+            }
+        }
+    }
+    // the 4 groups of a wave (lanes q, q + 16, q + 32, q + 48), then the 4 waves through LDS
+#pragma unroll
+    for (int s = 16; s <= 32; s <<= 1)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            a0[e] += __shfl_xor(a0[e], s);
+            a1[e] += __shfl_xor(a1[e], s);
+        }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s4[e] += __shfl_xor(s4[e], s);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane < 16) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            red[wv][4 * lane + e] = a0[e];
+            red[wv][kHeadCs + 4 * lane + e] = a1[e];
+        }
+    }
+    if (lane == 0)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[wv][2 * kHeadCs + e] = s4[e];
+    __syncthreads();
+    if ((int)threadIdx.x < kHeadCols) {
+        const int c = threadIdx.x;
+        partials[(size_t)blockIdx.x * kHeadCols + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+    }
+}
+
+// column c of the block partials -> dwo (c < 128), dbo (128, 129), the CE sums (130, 131; optional): block c, thread t adds
+// partials t, t + 256, ... in fp64, then a fixed tree
+__global__ __launch_bounds__(kThreads) void unet_head_bwd_reduce_kernel(const float* __restrict__ partials, int nblocks,
+                                                                        float* __restrict__ dwo, float* __restrict__ dbo,
+                                                                        float* __restrict__ sums) {
+    __shared__ double red[kThreads];
+    const int c = blockIdx.x;
+    double a = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += kThreads) a += (double)partials[(size_t)i * kHeadCols + c];
+    red[threadIdx.x] = a;
+    __syncthreads();
+    for (int s = kThreads / 2; s >= 1; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float v = (float)red[0];
+        if (c < 2 * kHeadCs) dwo[c] = v;
+        else if (c < 2 * kHeadCs + 2) dbo[c - 2 * kHeadCs] = v;
+        else if (sums) sums[c - 2 * kHeadCs - 2] = v;
+    }
+}
+
 unsigned ew_grid(size_t total) {
     const size_t b = (total + kThreads - 1) / kThreads;
     return (unsigned)(b < 1 ? 1 : (b > 65535 ? 65535 : b));
@@ -400,4 +610,56 @@ extern "C" int io_unet_head(const float* act, const float* wo, const float* bo, 
     if (rc || !partials) return rc;
     hipLaunchKernelGGL(unet_loss_reduce_kernel, dim3(1), dim3(kThreads), 0, st, partials, P * bx, loss_sums);
     return io_check_launch("unet_loss_reduce");
+}
+
+// ---- training (the backward launches of ops.max_pool_2x2 / ops.up2x_concat / ops.unet_head_loss) ---------------------------
+extern "C" int io_maxpool2x2_bwd(const float* dy, const float* x, const float* add, int N, int H, int W, int C, float* dx,
+                                 hipStream_t st) {
+    IO_REQUIRE(dy && x && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, IO_ERR_SHAPE,
+               "maxpool2x2_bwd: N=%d H=%d W=%d C=%d (C %% 4)", N, H, W, C);
+    IO_REQUIRE(H % 2 == 0 && W % 2 == 0, IO_ERR_SHAPE, "maxpool2x2_bwd: H=%d and W=%d must be even", H, W);
+    const size_t total = (size_t)N * (H / 2) * (W / 2) * (C / 4);
+    IoProfScope prof(IO_PROF_UNET, 0.0, 4.0 * total * 4 * (add ? 13.0 : 9.0), st);
+    hipLaunchKernelGGL(maxpool2x2_bwd_kernel, dim3(ew_grid(total)), dim3(kThreads), 0, st, dy, x, add, H, W, C / 4, total, dx);
+    return io_check_launch("maxpool2x2_bwd");
+}
+
+extern "C" int io_up2x_concat_bwd(const float* dcat, int N, int h, int w, int C2, int C1, float* dx2, float* dx1,
+                                  hipStream_t st) {
+    IO_REQUIRE(dcat && dx2 && dx1 && N > 0 && h > 0 && w > 0 && C1 > 0 && C2 > 0 && C1 % 4 == 0 && C2 % 4 == 0, IO_ERR_SHAPE,
+               "up2x_concat_bwd: N=%d h=%d w=%d C2=%d C1=%d (channel counts are multiples of 4)", N, h, w, C2, C1);
+    IO_REQUIRE((double)N * h * 2 < 2.0e9 && (double)w * 2 * (C1 + C2) < 2.0e9, IO_ERR_SHAPE, "up2x_concat_bwd: tensor too large");
+    const size_t t2 = (size_t)N * 2 * h * 2 * w * (C2 / 4), t1 = (size_t)N * h * w * (C1 / 4);
+    IoProfScope prof(IO_PROF_UNET, 0.0, 4.0 * (2.0 * t2 * 4 + 5.0 * t1 * 4), st);
+    hipLaunchKernelGGL(concat_split_kernel, dim3(ew_grid(t2)), dim3(kThreads), 0, st, dcat, C2 / 4, (C2 + C1) / 4, t2, dx2);
+    const int rc = io_check_launch("up2x_concat_bwd(split)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(up2x_bwd_kernel, dim3(ew_grid(t1)), dim3(kThreads), 0, st, dcat, h, w, C2 / 4, C1 / 4, t1, dx1);
+    return io_check_launch("up2x_concat_bwd");
+}
+
+extern "C" size_t io_unet_head_bwd_partial_floats(int P, int HW) {
+    if (P <= 0 || HW <= 0) return 0;
+    return (size_t)kHeadCols * (((size_t)P * HW + kThreads - 1) / kThreads);
+}
+
+extern "C" int io_unet_head_bwd(const float* act, const float* wo, const float* bo, const uint8_t* target, const float* eraser,
+                                int P, int HW, int Cs, float inmask_weight, float scale, const float* gscale, float* dx,
+                                float* dwo, float* dbo, float* loss_sums, float* partials, size_t partial_floats,
+                                hipStream_t st) {
+    IO_REQUIRE(act && wo && bo && target && eraser && dx && dwo && dbo && partials && P > 0 && HW > 0, IO_ERR_SHAPE,
+               "unet_head_bwd: P=%d HW=%d; every operand but gscale and loss_sums is required", P, HW);
+    IO_REQUIRE(Cs == kHeadCs, IO_ERR_SHAPE, "unet_head_bwd: Cs=%d, the kernel is written for a stored width of %d", Cs, kHeadCs);
+    const size_t total = (size_t)P * HW, nblocks = (total + kThreads - 1) / kThreads;
+    IO_REQUIRE(nblocks < (1u << 31), IO_ERR_SHAPE, "unet_head_bwd: too many blocks");
+    IO_REQUIRE(partial_floats >= io_unet_head_bwd_partial_floats(P, HW), IO_ERR_WORKSPACE, "unet_head_bwd: partials %zu < %zu floats",
+               partial_floats, io_unet_head_bwd_partial_floats(P, HW));
+    IoProfScope prof(IO_PROF_UNET, 8.0 * total * Cs, 4.0 * total * (2.0 * Cs + 2), st);
+    hipLaunchKernelGGL(unet_head_bwd_kernel, dim3((unsigned)nblocks), dim3(kThreads), 0, st, act, wo, bo, target, eraser, total,
+                       inmask_weight, scale, gscale, dx, partials);
+    const int rc = io_check_launch("unet_head_bwd");
+    if (rc) return rc;
+    hipLaunchKernelGGL(unet_head_bwd_reduce_kernel, dim3(kHeadCols), dim3(kThreads), 0, st, partials, (int)nblocks, dwo, dbo,
+                       loss_sums);
+    return io_check_launch("unet_head_bwd_reduce");
 }

@@ -1,5 +1,5 @@
 """Operator layer for graphs the fixed ResNet-50 executor (io_net_*) does not cover -- today the MiDaS branch
-(InstaDepthNet_od / _d, midas/midas_net.py:116-212).  Every function is a ``torch.autograd.Function`` whose forward
+(InstaDepthNet_od / _d, midas/midas_net.py:116-212) and the training step of PCNet-M's UNet (unet.py).  Every function is a ``torch.autograd.Function`` whose forward
 and backward are launches of libinstaorder_hip.so on **NHWC** tensors, fp32 or bf16 (the element type of the input
 selects the kernels; parameters and their gradients are always fp32); torch supplies memory, streams and the autograd
 tape only.  Filters are taken in the reference's OIHW layout (what ``state_dict`` holds) and re-laid out to the
@@ -17,7 +17,7 @@ import torch
 from . import _lib
 
 __all__ = ["conv2d", "conv_bn", "batch_norm", "max_pool_3x3s2", "avgpool_fc", "upsample2x", "bias_act", "relu", "add", "head1",
-           "nhwc_from_nchw", "nchw_from_nhwc"]
+           "max_pool_2x2", "up2x_concat", "unet_head_loss", "nhwc_from_nchw", "nchw_from_nhwc"]
 
 
 # bumped by whoever changes parameters behind torch's back (the HIP optimiser kernels update them in place without
@@ -837,6 +837,121 @@ class _Head1(torch.autograd.Function):
 
 def head1(x, w, b, relu):
     return _Head1.apply(x, w, b, relu)
+
+
+# ---- the UNet-only operators of PCNet-M (models/backbone/unet/unet_parts.py), fp32 ------------------------------------------
+def _chk32(t, name):
+    _chk(t, name)
+    if t.dtype != torch.float32:
+        raise NotImplementedError("instaorder_amd.ops: %s must be fp32 (the UNet operators have no bf16 form)" % name)
+
+
+class _MaxPool2x2(torch.autograd.Function):
+    """nn.MaxPool2d(2) (unet_parts.py:36).  fork: x comes back as a second output (an alias), as in _ConvBn: the pooled tensor
+    of a ``down`` block is also the skip tensor of an ``up`` block, and with the skip routed through the alias its gradient
+    arrives HERE and rides in the `add` operand of io_maxpool2x2_bwd instead of an accumulation pass of the autograd engine
+    over a full-resolution tensor."""
+
+    @staticmethod
+    def forward(ctx, x, fork):
+        _chk32(x, "x")
+        N, H, W_, Cc = x.shape
+        out = torch.empty((N, H // 2, W_ // 2, Cc), device=x.device, dtype=x.dtype)
+        _lib.check(_L().io_maxpool2x2_fwd(_p(x), N, H, W_, Cc, _p(out), _st()), "io_maxpool2x2_fwd")
+        ctx.save_for_backward(x)
+        return (out, x) if fork else out
+
+    @staticmethod
+    def backward(ctx, dy, dskip=None):
+        x, = ctx.saved_tensors
+        N, H, W_, Cc = x.shape
+        if dy is None:                    # (only the skip path was used)
+            return dskip, None
+        dx = torch.empty_like(x)
+        add = dskip.contiguous() if dskip is not None else None
+        _lib.check(_L().io_maxpool2x2_bwd(_p(dy.contiguous()), _p(x), _p(add), N, H, W_, Cc, _p(dx), _st()),
+                   "io_maxpool2x2_bwd")
+        return dx, None
+
+
+def max_pool_2x2(x, fork=False):
+    """nn.MaxPool2d(2) on [N,H,W,C] (H, W even).  ``fork=True`` (x requires a gradient): returns ``(pooled, x_alias)``; route
+    every other use of x through ``x_alias`` (see _MaxPool2x2)."""
+    fork = bool(fork and torch.is_grad_enabled() and x.requires_grad)
+    return _MaxPool2x2.apply(x, fork)
+
+
+class _Up2xConcat(torch.autograd.Function):
+    """cat([x2, upsample x2 (bilinear, align_corners=True) of x1], channel) (unet_parts.py:54-71, sizes that meet without F.pad)"""
+
+    @staticmethod
+    def forward(ctx, x2, x1):
+        _chk32(x2, "x2")
+        _chk32(x1, "x1")
+        n, h, w, c1 = x1.shape
+        c2 = x2.shape[3]
+        if tuple(x2.shape[:3]) != (n, 2 * h, 2 * w):
+            raise ValueError("up2x_concat: x2 %s is not twice x1 %s" % (tuple(x2.shape), tuple(x1.shape)))
+        cat = torch.empty((n, 2 * h, 2 * w, c2 + c1), device=x1.device)
+        _lib.check(_L().io_up2x_concat_fwd(_p(x2), _p(x1), n, h, w, c2, c1, _p(cat), _st()), "io_up2x_concat_fwd")
+        ctx.geom = (n, h, w, c2, c1)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        n, h, w, c2, c1 = ctx.geom
+        dx2 = torch.empty((n, 2 * h, 2 * w, c2), device=dcat.device)
+        dx1 = torch.empty((n, h, w, c1), device=dcat.device)
+        _lib.check(_L().io_up2x_concat_bwd(_p(dcat.contiguous()), n, h, w, c2, c1, _p(dx2), _p(dx1), _st()), "io_up2x_concat_bwd")
+        return dx2, dx1
+
+
+def up2x_concat(x2, x1):
+    return _Up2xConcat.apply(x2, x1)
+
+
+class _UnetHeadLoss(torch.autograd.Function):
+    """The 1x1 head (outconv, unet_parts.py:74-81) and MaskWeightedCrossEntropyLoss (models/losses.py:60-88) over
+    ``world_size`` as ONE node on the last activation x[N,H,W,Cs]: forward = io_unet_head in loss mode (no logits in memory),
+    backward = io_unet_head_bwd, the incoming scalar gradient read on the device.  w [2,C,1,1] with the C real channels
+    stored first; the gradients come back in the parameters' shapes."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, mask, eraser, target, inmask_weight, world_size):
+        _chk32(x, "x")
+        N, H, W_, Cs = x.shape
+        Cr = w.shape[1]
+        wo = torch.zeros((2, Cs), device=x.device)
+        wo[:, :Cr] = w.detach().reshape(2, Cr)
+        bo = b.detach().float().contiguous()
+        L = _L()
+        nf = int(L.io_unet_head_partial_floats(N, H * W_))
+        partials, sums = torch.empty(nf, device=x.device), torch.empty(2, device=x.device)
+        _lib.check(L.io_unet_head(_p(x), _p(wo), _p(bo), _p(mask), _p(eraser), _p(target), N, H * W_, Cs, 0.5, None, None, None,
+                                  _p(partials), nf, _p(sums), _st()), "io_unet_head")
+        ctx.save_for_backward(x, wo, bo, eraser, target)
+        ctx.cfg = (float(inmask_weight), 1.0 / (N * H * W_ * world_size), tuple(w.shape))
+        return (float(inmask_weight) * sums[0] + 1.0 * sums[1]) / (N * H * W_) / world_size
+
+    @staticmethod
+    def backward(ctx, dl):
+        x, wo, bo, eraser, target = ctx.saved_tensors
+        iw, scale, wshape = ctx.cfg
+        N, H, W_, Cs = x.shape
+        L = _L()
+        nf = int(L.io_unet_head_bwd_partial_floats(N, H * W_))
+        partials = torch.empty(nf, device=x.device)
+        dx = torch.empty_like(x)
+        dwo, dbo = torch.empty((2, Cs), device=x.device), torch.empty(2, device=x.device)
+        _lib.check(L.io_unet_head_bwd(_p(x), _p(wo), _p(bo), _p(target), _p(eraser), N, H * W_, Cs, iw, scale,
+                                      _p(dl.float().contiguous()), _p(dx), _p(dwo), _p(dbo), None, _p(partials), nf, _st()),
+                   "io_unet_head_bwd")
+        return dx, dwo[:, :wshape[1]].reshape(wshape).contiguous(), dbo, None, None, None, None, None
+
+
+def unet_head_loss(x, w, b, mask, eraser, target, inmask_weight, world_size=1):
+    """-> the 0-d loss.  mask, eraser: fp32 [N,H,W]; target: uint8 [N,H,W] in {0, 1}; all contiguous, on the device."""
+    return _UnetHeadLoss.apply(x, w, b, mask, eraser, target, inmask_weight, world_size)
 
 
 class _SmoothLoss(torch.autograd.Function):

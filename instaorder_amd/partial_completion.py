@@ -1,4 +1,4 @@
-"""PartialCompletionMask (PCNet-M) -- evaluation of a trained checkpoint (models/partial_completion_mask.py:12-114).
+"""PartialCompletionMask (PCNet-M): evaluation of a checkpoint and the training step (models/partial_completion_mask.py:12-126).
 
 ``set_input(rgb, mask, eraser, target)`` + ``forward_only(ret_loss=True)`` reproduce the reference's validation pass: the
 UNet on cat([mask, eraser]), ``comp`` = argmax with the visible mask pasted outside the eraser, and
@@ -8,11 +8,15 @@ MaskWeightedCrossEntropyLoss (models/losses.py:60-88)
 
 with CE_in / CE_out the cross-entropy SUMS over the pixels inside / outside the eraser -- two numbers the head kernel
 returns (io_unet_head, loss mode; per-block partials added in a fixed order).  The order-recovery rule on top of the same
-network is ``inference.infer_order``.  Training (``step``), the eraser-synthesising dataset and amodal completion are not
-in the package.  The optimiser and the checkpoint I/O come from SingleStageModel unchanged.
+network is ``inference.infer_order``.  ``step()`` is the reference's training step, eager and fp32: the train-mode UNet of
+unet.py (autograd nodes of ops.py), the same loss through the fused head node (io_unet_head forward, io_unet_head_bwd
+backward), then the optimiser of SingleStageModel (FlatSGD / FlatAdam, ``clip_grad_norm``).  ``forward_only`` wants eval
+mode (the reference's trainer switches before it validates).  The eraser-synthesising dataset and amodal completion are
+not in the package.  The optimiser and the checkpoint I/O come from SingleStageModel unchanged.
 """
 import torch
 
+from . import distributed_utils
 from .single_stage_model import SingleStageModel
 
 
@@ -59,4 +63,21 @@ class PartialCompletionMask(SingleStageModel):
         return ret_tensors, {"loss": loss}
 
     def step(self):
-        raise NotImplementedError("training PCNet-M is not in the package yet")
+        """One training step, the reference's in its order (partial_completion_mask.py:116-126): forward on
+        cat([mask, eraser]) (no erase, no category scale), the loss over world_size, zero_grad, backward, the gradient
+        exchange, the update.  Eager: one launch per node, no graph capture."""
+        if self.net.dtype != "fp32":
+            raise NotImplementedError("PartialCompletionMask.step: dtype=%r is not in the package (fp32 only; bf16 "
+                                      "training of the UNet is not written)." % (self.net.dtype,))
+        if getattr(self, "mask", None) is None:
+            # the reference's trainer feeds set_input from PartialCompDataset, which is deliberately out of the package
+            raise NotImplementedError("PartialCompletionMask.step: no input has been set, and the package has no "
+                                      "eraser-synthesising dataset of its own -- self-fed training PCNet-M is not in the "
+                                      "package yet; call set_input(rgb, mask, eraser, target) before every step().")
+        loss = self.net.loss_train(self.mask, self.eraser, self.target, self.inmask_weight, self.world_size)
+        self.optim.zero_grad()
+        loss.backward()
+        if self.world_size > 1:
+            distributed_utils.average_gradients(self.model)
+        self.optim.step()
+        return {"loss": loss.detach()}

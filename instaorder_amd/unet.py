@@ -1,4 +1,5 @@
-"""The UNet of PCNet-M (models/backbone/unet/unet_model.py:51-91, unet_parts.py) -- inference only.
+"""The UNet of PCNet-M (models/backbone/unet/unet_model.py:51-91, unet_parts.py): the folded eval-mode plan and the
+train-mode plan of autograd nodes ("Training" at the end of this text).
 
 ``UNet(in_channels, w, n_classes=2)`` is an ``nn.Module`` whose ``state_dict()`` has exactly the reference's keys, shapes
 and dtypes (``inc.conv.conv.{0,1,3,4}.*``, ``down{1..4}.mpconv.1.conv.*``, ``up{1..4}.conv.conv.*``,
@@ -21,6 +22,20 @@ exactly 0, and max-pooling / interpolation keep them 0.  The concatenation of an
 (``_stored_index``): real channel c of segment k sits at sum(stored of the segments before k) + (c - sum(real before k)).
 unet1 (16-channel tensors stored as 32) exercises the gap; unet2's tensors have none.  The network input (2 planes) is
 stored as 8 channels in front of the 32-channel kernel and as 32 in front of the dense launcher.
+
+Training.  In ``train()`` mode ``forward(x)`` returns logits that carry autograd, and ``loss_train`` (what
+``PartialCompletionMask.step`` calls) the loss through the fused head node.  The plan is the same network strung from
+``ops.*`` nodes on the module's own parameters and BatchNorm buffers: ops.conv_bn / ops.conv2d + ops.batch_norm (chosen by
+``bn_route``, by shape, in one place), ops.max_pool_2x2, ops.up2x_concat, ops.unet_head_loss.  The route switch does not
+apply: every tensor, the network input included, is stored at its real width rounded up to 64 (``plan(False, cin=64)``),
+where the dense launchers serve forward, data gradient and filter gradient.  ``_TrainFilter`` scatters a filter to that
+layout (zero padding filters; the concatenation keeps ``_stored_index``'s segments) and slices its gradient back; gamma and
+beta are zero-padded, so a padding channel is 0 * rstd + 0 = exactly 0 forward and gets exactly 0 gradient.
+The reference's 3x3 convolutions carry a bias in front of a batch-statistics BatchNorm: it cancels in the output and
+shifts only the batch mean.  It is not added; ``running_mean`` advances by momentum * bias on top of what the statistics
+node wrote (the mean of conv + bias); and the bias gets a gradient of exact zeros (the reference's is rounding noise),
+so weight decay and momentum move it as they do there.  The statistics nodes bump ops.WEIGHTS_EPOCH: the eval plan
+re-folds after training.
 """
 import ctypes as C
 
@@ -31,6 +46,7 @@ import torch.nn as nn
 from . import _lib, ops
 
 _CO32_INPUTS = (8, 32, 64, 128)          # stored input widths io_conv3x3_co32_fwd takes
+TRAIN_INPUT = 64                         # stored width of the network input on the training route
 
 
 def set_co32(on):
@@ -116,6 +132,51 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+class _TrainFilter(torch.autograd.Function):
+    """The training operand of a 3x3 convolution in front of a batch-statistics BatchNorm: OIHW [Co,Ci,3,3] scattered to
+    [co_st, ci_st, 3, 3] (zero padding filters, input channels at the stored positions ``idx``).  The gradient comes back
+    sliced to the parameter's shape.  The convolution's bias is an input only to receive its gradient: exact zeros -- it
+    cancels under batch statistics (module text, "Training")."""
+
+    @staticmethod
+    def forward(ctx, w, bias, idx, co_st, ci_st):
+        co = w.shape[0]
+        out = w.new_zeros((co_st, ci_st, 3, 3))
+        out[:co, idx] = w.detach()
+        ctx.idx, ctx.co = idx, co
+        ctx.bias_like = bias.detach()
+        return out
+
+    @staticmethod
+    def backward(ctx, dw):
+        return dw[:ctx.co, ctx.idx].contiguous(), torch.zeros_like(ctx.bias_like), None, None, None
+
+
+class HipTrainOps(object):
+    """the operators UNet.features_train strings together, as launches (NHWC fp32 on the GPU)"""
+
+    @staticmethod
+    def pack_input(m1, m2, cs):
+        N, H, W = m1.shape
+        x = torch.empty((N, H, W, cs), device=m1.device)
+        _lib.check(_lib.lib().io_unet_pack_input(_p(m1), _p(m2), None, N, H * W, cs, 0, _p(x), ops._st()), "io_unet_pack_input")
+        return x
+
+    @staticmethod
+    def conv_bn_relu(x, w, gamma, beta, rm, rv, route):
+        if route == "fused":
+            return ops.conv_bn(x, w, gamma, beta, rm, rv, 1, 1, 1, True, relu=True)
+        return ops.batch_norm(ops.conv2d(x, w, 1, 1), gamma, beta, rm, rv, True, relu=True)
+
+    @staticmethod
+    def max_pool_2x2(x):
+        return ops.max_pool_2x2(x, fork=True)
+
+    @staticmethod
+    def up2x_concat(x2, x1):
+        return ops.up2x_concat(x2, x1)
+
+
 class UNet(nn.Module):
     def __init__(self, in_channels=3, w=4, n_classes=2, dtype="fp32"):
         super(UNet, self).__init__()
@@ -143,14 +204,15 @@ class UNet(nn.Module):
     def input_stored(self, co32):
         return 8 if (co32 and self.width[0] <= 32) else 32
 
-    def plan(self, co32):
+    def plan(self, co32, cin=None):
         """[(block index, conv index, segments of the input, real Co, stored Co, runs the 32-channel kernel)] of the 18
-        3x3 convolutions, then the layout of the head's input"""
+        3x3 convolutions, then the layout of the head's input.  ``cin``: stored width of the network input (default: what
+        the eval route of ``co32`` packs)."""
         c = self.width
         out_real = [c[0], c[1], c[2], c[3], c[3], c[2], c[1], c[0], c[0]]
         seg = lambda r: (r, stored(r, co32))     # noqa: E731
         skips = [seg(c[0]), seg(c[1]), seg(c[2]), seg(c[3])]              # x1 .. x4
-        first = [[(self.in_channels, self.input_stored(co32))], [seg(c[0])], [seg(c[1])], [seg(c[2])], [seg(c[3])],
+        first = [[(self.in_channels, cin or self.input_stored(co32))], [seg(c[0])], [seg(c[1])], [seg(c[2])], [seg(c[3])],
                  [skips[3], seg(c[3])], [skips[2], seg(c[2])], [skips[1], seg(c[1])], [skips[0], seg(c[0])]]
         steps = []
         for b in range(9):
@@ -207,9 +269,10 @@ class UNet(nn.Module):
                        "io_conv2d_fwd_bias_dt")
         return y
 
-    def _check(self):
-        if self.training:
-            raise NotImplementedError("UNet.forward in training mode is not in the package yet (eval() only).")
+    def _check(self, training=False):
+        if self.training != training:
+            raise RuntimeError("UNet: this path runs in %s mode, the module is in %s mode"
+                               % (("eval", "train")[training], ("eval", "train")[self.training]))
         if self.dtype != "fp32":
             raise NotImplementedError("UNet: dtype=%r is not in the package yet (fp32 only)." % (self.dtype,))
         if self.in_channels != 2:
@@ -267,11 +330,95 @@ class UNet(nn.Module):
                                   _p(counts), _p(logits), _p(partials), nf, _p(sums), st), "io_unet_head")
         return dict(comp=comp, counts=counts, logits=logits, loss_sums=sums)
 
+    # ---- training: the same network composed from autograd nodes of ops.py (module text, "Training") --------------------------
+    @staticmethod
+    def bn_route(rows):
+        """how a conv -> BatchNorm -> ReLU unit runs in training, by its rows per BatchNorm group -- THE place that decides:
+        'fused' = ops.conv_bn (statistics in the convolution's epilogue; its contract: whole 128-row tiles),
+        'split' = ops.conv2d, then ops.batch_norm"""
+        return "fused" if rows % 128 == 0 else "split"
+
+    def _unit_train(self, x, conv, bn, segs, co_st, impl):
+        """relu(bn(conv(x))) with batch statistics on the stored layout; the module's running estimates advanced as the
+        reference's are"""
+        co = conv.weight.shape[0]
+        idx, ci_st = _stored_index(segs)
+        assert x.shape[3] == ci_st, (tuple(x.shape), ci_st)
+        w = _TrainFilter.apply(conv.weight, conv.bias, torch.from_numpy(idx).to(x.device), co_st, ci_st)
+        gamma, beta = (nn.functional.pad(t, (0, co_st - co)) for t in (bn.weight, bn.bias))
+        # the statistics nodes advance these in place; the padding channels (mean 0, variance 0) are dropped below
+        rm, rv = x.new_zeros(co_st), x.new_ones(co_st)
+        rm[:co], rv[:co] = bn.running_mean, bn.running_var
+        out = impl.conv_bn_relu(x, w, gamma, beta, rm, rv, self.bn_route(x.shape[0] * x.shape[1] * x.shape[2]))
+        with torch.no_grad():
+            # the node saw conv(x) without the bias: the mean of conv(x) + bias is that mean + bias
+            bn.running_mean.copy_(rm[:co]).add_(conv.bias, alpha=bn.momentum)
+            bn.running_var.copy_(rv[:co])
+            bn.num_batches_tracked += 1
+        return out
+
+    def features_train(self, m1, m2, impl=None):
+        """m1, m2: [N,S,S] fp32 planes on the GPU -> the last activation [N,S,S,64] with its autograd graph.  ``impl``: the
+        four operators the plan is strung from (default: HipTrainOps, the launches; the CPU tests pass torch functions of
+        the same signatures to check the stored-layout algebra without a GPU)."""
+        self._check(training=True)
+        if impl is None:
+            _lib.require_gpu()
+            impl = HipTrainOps
+        N, H, W = m1.shape
+        if H % 16 or W % 16:
+            raise ValueError("UNet: the patch is %d x %d; both sides must be multiples of 16" % (H, W))
+        for blk in self._blocks():
+            for k in (1, 4):
+                if blk.conv[k].momentum is None or not blk.conv[k].track_running_stats:
+                    raise NotImplementedError("UNet: BatchNorm with momentum=None / without running statistics")
+        steps, head_segs = self.plan(False, cin=TRAIN_INPUT)
+        blocks = self._blocks()
+        x = impl.pack_input(m1, m2, TRAIN_INPUT)
+
+        def double(x, b):
+            for k in (0, 1):
+                _, ck, segs, _, co_st, _ = steps[2 * b + k]
+                x = self._unit_train(x, blocks[b].conv[ck], blocks[b].conv[ck + 1], segs, co_st, impl)
+            return x
+
+        x = double(x, 0)
+        skips = []
+        for b in range(1, 5):
+            pooled, skip = impl.max_pool_2x2(x)       # (the skip's gradient rides in the pool backward's `add`)
+            skips.append(skip)
+            x = double(pooled, b)
+        for b in range(5, 9):
+            x = double(impl.up2x_concat(skips.pop(), x), b)
+        assert head_segs[0][1] == x.shape[3]
+        return x
+
+    def loss_train(self, mask, eraser, target, inmask_weight, world_size=1):
+        """training forward + MaskWeightedCrossEntropyLoss / world_size as the fused head node (no logits in memory):
+        mask, eraser [N,1,S,S] fp32, target [N,S,S] in {0, 1} -> the 0-d loss, carrying autograd"""
+        m1, m2 = mask[:, 0].contiguous().float(), eraser[:, 0].contiguous().float()
+        x = self.features_train(m1, m2)
+        return ops.unet_head_loss(x, self.outc.conv.weight, self.outc.conv.bias, m1, m2, target.to(torch.uint8).contiguous(),
+                                  inmask_weight, world_size)
+
+    def _forward_train(self, x):
+        feat = self.features_train(x[:, 0].contiguous().float(), x[:, 1].contiguous().float())
+        w = self.outc.conv.weight
+        wp = nn.functional.pad(w, (0, 0, 0, 0, 0, feat.shape[3] - w.shape[1]))       # [2, 64, 1, 1]: real channels first
+        logits = ops.bias_act(ops.conv2d(feat, wp, 1, 0, co_pad=True), self.outc.conv.bias)
+        return logits[..., :2].permute(0, 3, 1, 2).contiguous()
+
     def forward(self, x):
-        """[N,2,S,S] -> logits [N,2,S,S] (the reference's ``UNet.forward(x)``; it takes no image)"""
-        self._check()
+        """[N,2,S,S] -> logits [N,2,S,S] (the reference's ``UNet.forward(x)``; it takes no image).  In train() mode the
+        logits carry autograd and the BatchNorm buffers advance."""
+        self._check(training=self.training)
+        if self.training and not x.is_cuda:
+            raise NotImplementedError("UNet.forward in training mode is written for the GPU only: the input must be a "
+                                      "cuda tensor (there is no CPU fallback).")
         if not x.is_cuda:
             raise RuntimeError("instaorder_amd.unet: the input must be on the GPU (there is no CPU fallback)")
+        if self.training:
+            return self._forward_train(x)
         out = self.run(x[:, 0], x[:, 1], want_logits=True)
         return out["logits"].permute(0, 3, 1, 2).contiguous()
 
